@@ -10,12 +10,18 @@ Multi-GPU: polynomials are independent, so each rank owns its o
 shard (weak scaling) and there is no data-path collective; torch.distributed (RCCL) is used only
 for the start/stop barriers and the max-over-ranks time.
 
-The second half of the metric, "PBS/sec @ shortint default params" (config 4), is measured in the
+A plain run does only what the headline needs: set up, W warmup steps, K timed steps, the outputs of the last
+step to ``--dump-outputs DIR`` when asked, one JSON result line.  Everything else lives behind ``--full``.
+
+With ``--full`` the second half of the metric, "PBS/sec @ shortint default params" (config 4), is measured in the
 same run and reported under "pbs": one step = a batch of 4096 programmable bootstraps per GPU at
 the PARAM_MESSAGE_2_CARRY_2 shape (n=918, k=1, N=2048, base 2^23, l=1, native 2^64 ciphertexts
-through the BNF NTT algorithm, ntt64_bnf_pbs.rs:469-540), one fused kernel launch.
+through the BNF NTT algorithm, ntt64_bnf_pbs.rs:469-540), one fused kernel launch; so are the cold-start and
+steady-state loops, the per-direction split, the other legs, the host path and the CPU baselines, and the
+whole record is written to a file.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-pbs]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                        [--full [--no-cpu-baseline] [--no-pbs] [--no-shapes]]
 
 ``--gpus N`` with N > 1 outside a torch.distributed launch re-launches this script under
 ``python -m torch.distributed.run --nproc-per-node N`` (as a child process, before anything touches the
@@ -43,6 +49,7 @@ VALU_CYCLES = {"fwd": 13631.3, "inv": 14158.8, "pbs_step": 35057.4, "pbs_sol_ste
 SIMDS, PEAK_CLOCK_HZ = 256 * 4, 2.4e9
 # PARAM_MESSAGE_2_CARRY_2 shape (ks_pbs.rs:29-47)
 PBS_N_LWE, PBS_BASE_LOG, PBS_LEVEL, PBS_BATCH = 918, 23, 1, 4096
+DUMP_ROWS = 1024  # --dump-outputs: 1024 polynomials x N x 2 float64 arrays = 32 MiB at N = 2048
 
 
 def parse():
@@ -53,6 +60,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=10000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: cold-start and steady-state loops, the per-direction "
+                         "split, the component legs, the host path, the CPU baselines, and write the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left in the batch (a fixed seeded sample of "
+                         f"at most {DUMP_ROWS} polynomials) as DIR/<name>.npy, float64 holding the low / high 32 bits")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg")
     ap.add_argument("--no-pbs", action="store_true", help="skip the config-4 PBS leg")
@@ -1089,6 +1102,29 @@ def load_traffic():
         return None
 
 
+def dump_rows(batch: int):
+    """The polynomials --dump-outputs keeps: all of a small batch, else DUMP_ROWS of them drawn once from SEED."""
+    import numpy as np
+
+    if batch <= DUMP_ROWS:
+        return np.arange(batch)
+    return np.sort(np.random.default_rng(SEED).choice(batch, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(dirpath: str, name: str, words) -> list:
+    """Write a uint64 array as two float64 arrays, `<name>_lo32.npy` and `<name>_hi32.npy` (float64 holds a 32-bit
+    half exactly, not a 64-bit residue), so two builds compare bit for bit.  Returns the paths written."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    words = np.ascontiguousarray(words).view(np.uint64)
+    paths = []
+    for part, half in (("lo32", words & np.uint64(0xFFFFFFFF)), ("hi32", words >> np.uint64(32))):
+        paths.append(os.path.join(dirpath, f"{name}_{part}.npy"))
+        np.save(paths[-1], half.astype(np.float64))
+    return paths
+
+
 def relaunch_distributed(n: int) -> int:
     """One process per GPU: run this script under torch.distributed.run with N ranks (a child process;
     this process has not touched the GPU) and return its exit status."""
@@ -1172,12 +1208,16 @@ def main():
     # Cold start: the K steps straight from an idle GPU, before any other work (the engine clock is still ramping:
     # reported, not the headline).  The component legs then keep the GPU busy for several seconds, and the headline
     # below is the same W + K steps at the clock the chip holds under sustained load.
-    cold_el, cold_launch = headline(K, args.warmup)
-    cold = {"value": world * batch * K / cold_el, "ms_per_step": cold_el / K * 1e3, "timed_launch_ms": cold_launch,
-            "roofline_frac": bytes_launch / (cold_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "note": "the same W + K steps measured first, from an idle GPU, before any leg ran"}
+    # All of that is --full's; a plain run goes straight to the headline's W + K steps.
+    full = args.full
+    cold = None
+    if full:
+        cold_el, cold_launch = headline(K, args.warmup)
+        cold = {"value": world * batch * K / cold_el, "ms_per_step": cold_el / K * 1e3, "timed_launch_ms": cold_launch,
+                "roofline_frac": bytes_launch / (cold_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "the same W + K steps measured first, from an idle GPU, before any leg ran"}
     legs = {}
-    if not args.no_pbs:
+    if full and not args.no_pbs:
         if not args.no_shapes:
             legs["pbs_shapes"] = {name: bench_pbs_shape(name, args, eng, torch, dev, world, barrier, dist)
                                   for name in SHAPE_LEGS}
@@ -1200,43 +1240,55 @@ def main():
 
     elapsed, launch_ms = headline(K, args.warmup)
 
-    # steady state: a time-based loop of >= --steady-seconds after the timed region (same stream, same buffer)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ss_k = max(1, int(args.steady_seconds / max(2 * launch_ms * 1e-3, 1e-6)))
-    if dist is not None:
-        ss_k = int(eng.multi_gpu.max_over_ranks(float(ss_k), dev))
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    e0.record(work)
-    for _ in range(ss_k):
-        plan.fwd(buf)
-        plan.inv(buf)
-    e1.record(work)
-    torch.cuda.synchronize()
-    barrier()
-    ss_el = time.perf_counter() - t0
-    if dist is not None:
-        ss_el = eng.multi_gpu.max_over_ranks(ss_el, dev)
-    ss_launch = e0.elapsed_time(e1) / (2 * ss_k)
-    steady = {"value": world * batch * ss_k / ss_el, "steps": ss_k, "seconds": ss_el, "timed_launch_ms": ss_launch,
-              "roofline_frac": bytes_launch / (ss_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
-              "note": "fwd+inv loop of >= --steady-seconds right after the timed region"}
+    # --dump-outputs: the sampled polynomials as the last timed step left them (a device copy: --full's loops below
+    # go on transforming the batch in place)
+    last = None
+    if args.dump_outputs:
+        last = buf.index_select(0, torch.from_numpy(dump_rows(batch)).to(dev))
 
-    # per-direction split (informational), from a separate loop of back-to-back launches of one kernel;
-    # the roofline below uses the timed launches
+    def steady_state():
+        """A time-based loop of >= --steady-seconds after the timed region (same stream, same buffer)."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ss_k = max(1, int(args.steady_seconds / max(2 * launch_ms * 1e-3, 1e-6)))
+        if dist is not None:
+            ss_k = int(eng.multi_gpu.max_over_ranks(float(ss_k), dev))
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(work)
+        for _ in range(ss_k):
+            plan.fwd(buf)
+            plan.inv(buf)
+        e1.record(work)
+        torch.cuda.synchronize()
+        barrier()
+        ss_el = time.perf_counter() - t0
+        if dist is not None:
+            ss_el = eng.multi_gpu.max_over_ranks(ss_el, dev)
+        ss_launch = e0.elapsed_time(e1) / (2 * ss_k)
+        return {"value": world * batch * ss_k / ss_el, "steps": ss_k, "seconds": ss_el, "timed_launch_ms": ss_launch,
+                "roofline_frac": bytes_launch / (ss_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "fwd+inv loop of >= --steady-seconds right after the timed region"}
+
     split_k = min(K, 500)
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    e0.record(work)
-    for k in range(split_k):
-        plan.fwd(buf)
-    e1.record(work)
-    for k in range(split_k):
-        plan.inv(buf)
-    e2.record(work)
-    torch.cuda.synchronize()
-    fwd_ms = e0.elapsed_time(e1) / split_k
-    inv_ms = e1.elapsed_time(e2) / split_k
+
+    def direction_split():
+        """Per-direction split (informational), from a separate loop of back-to-back launches of one kernel;
+        the roofline below uses the timed launches."""
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record(work)
+        for k in range(split_k):
+            plan.fwd(buf)
+        e1.record(work)
+        for k in range(split_k):
+            plan.inv(buf)
+        e2.record(work)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / split_k, e1.elapsed_time(e2) / split_k
+
+    if full:
+        steady = steady_state()
+        fwd_ms, inv_ms = direction_split()
     achieved = bytes_launch / (launch_ms * 1e-3) / 1e9
 
     units = world * batch * K
@@ -1260,21 +1312,13 @@ def main():
             "batch_per_gpu": batch,
             "global_batch": batch * world,
             "parallelism": f"independent shards x{world} (no data-path collective)",
-            "order": "cold_start (W + K steps from idle) -> component legs (external product last) -> headline "
-                     "(W + K steps) -> steady_state",
+            "order": ("cold_start (W + K steps from idle) -> component legs (external product last) -> headline "
+                      "(W + K steps) -> steady_state") if full else "headline alone (W + K steps); --full runs the rest",
             "hip_runtime": eng._lib.hip_runtimes(),
             "build": eng._lib.build_provenance(),
         },
-        "kernels": {"timed_launch_ms": launch_ms, "fwd_ms": fwd_ms, "inv_ms": inv_ms,
-                    "note": "timed_launch_ms: HIP events around the timed region / (2 K launches); "
-                            f"fwd_ms / inv_ms: {split_k} back-to-back launches of one direction after it"},
-        # the binding limit: integer VALU issue (SIMD cycles per launch at the peak clock vs measured)
-        "valu_bound": {
-            kind: {"issue_cycles_per_poly": VALU_CYCLES[kind],
-                   "model_ms": batch * VALU_CYCLES[kind] / SIMDS / PEAK_CLOCK_HZ * 1e3,
-                   "measured_ms": ms,
-                   "frac": batch * VALU_CYCLES[kind] / SIMDS / PEAK_CLOCK_HZ * 1e3 / ms}
-            for kind, ms in (("fwd", fwd_ms), ("inv", inv_ms))},
+        "kernels": {"timed_launch_ms": launch_ms,
+                    "note": "timed_launch_ms: HIP events around the timed region / (2 K launches)"},
         "roofline": {
             "bound": "hbm",
             "kernel": "ntt_tw_body_kernel fwd / inv (average over the 2 K timed launches)",
@@ -1288,10 +1332,21 @@ def main():
             "algorithmic_bytes_per_launch": bytes_launch,
         },
         "cpu_baseline": None,
-        "cold_start": cold,
-        "steady_state": steady,
     }
-    if rank == 0 and world == 1:
+    if full:
+        out["kernels"].update(fwd_ms=fwd_ms, inv_ms=inv_ms,
+                              note=out["kernels"]["note"] + f"; fwd_ms / inv_ms: {split_k} back-to-back launches of "
+                                                            "one direction after it")
+        # the binding limit: integer VALU issue (SIMD cycles per launch at the peak clock vs measured)
+        out["valu_bound"] = {
+            kind: {"issue_cycles_per_poly": VALU_CYCLES[kind],
+                   "model_ms": batch * VALU_CYCLES[kind] / SIMDS / PEAK_CLOCK_HZ * 1e3,
+                   "measured_ms": ms,
+                   "frac": batch * VALU_CYCLES[kind] / SIMDS / PEAK_CLOCK_HZ * 1e3 / ms}
+            for kind, ms in (("fwd", fwd_ms), ("inv", inv_ms))}
+        out["cold_start"] = cold
+        out["steady_state"] = steady
+    if full and rank == 0 and world == 1:
         out["host_path"] = bench_host_path(eng, torch)
         if not args.no_pbs and not args.no_shapes:  # (it runs the shape-generic f64 engine, as the shape legs do)
             out["default_stream"] = bench_default_stream(eng, torch, dev, work)
@@ -1299,7 +1354,7 @@ def main():
     for name in LEG_ORDER:
         if name in legs:
             out[name] = legs[name]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         if not args.no_pbs:
             out["ext_product"]["cpu_baseline"] = cpu_baseline_ext(min(args.cpu_seconds, 4.0))
@@ -1317,8 +1372,11 @@ def main():
             for name, (n_, k_, nl_, bl_, lv_, _) in (SHAPE_LEGS.items() if not args.no_shapes else ()):
                 out["pbs_shapes_fft"][name]["cpu_numpy_restatement"] = cpu_baseline_pbs_fft(
                     n_, k_, nl_, bl_, lv_, min(args.cpu_seconds, 3.0))
+    if last is not None:
+        # every rank writes its own shard's sample; rank 0's files carry the plain names
+        dump_outputs(args.dump_outputs, "ntt_fwd_inv" if rank == 0 else f"ntt_fwd_inv_rank{rank}", last.cpu().numpy())
     if rank == 0:
-        full_path = write_full_record(out)
+        full_path = write_full_record(out) if full else None
         # the driver parses the LAST stdout line and keeps only the tail: one compact line (<= LINE_MAX_BYTES)
         print(json.dumps(compact_line(out, full_path)), flush=True)
     if dist is not None:
@@ -1360,7 +1418,7 @@ def compact_line(out, full_path=None):
                                                 "traffic_source", "algorithmic_bytes_per_launch", "kernel")}
     line["cpu_baseline"] = out.get("cpu_baseline")
     kern = out.get("kernels") or {}
-    line["kernels"] = {k: kern.get(k) for k in ("timed_launch_ms", "fwd_ms", "inv_ms")}
+    line["kernels"] = {k: kern[k] for k in ("timed_launch_ms", "fwd_ms", "inv_ms") if k in kern}  # (the split: --full)
     line["valu_bound_frac"] = {k: v.get("frac") for k, v in (out.get("valu_bound") or {}).items()}
     # the sustained rate beside the K-step burst: the >= 1 s loop right after the timed region, and
     # the same K steps from an idle GPU

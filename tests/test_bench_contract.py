@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -47,6 +49,67 @@ def test_gpus_flag_launches_one_rank_per_gpu(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     with pytest.raises(SystemExit, match="WORLD_SIZE=2"):
         bench.main()
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """`--full` and `--dump-outputs` exist and are off unless given; the flags of the legs still parse beside them."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and (args.steps, args.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--no-shapes", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d" and args.no_cpu_baseline and args.no_shapes
+
+
+def test_dump_outputs_is_exact_and_bounded(tmp_path):
+    """The dump holds every bit of its u64 residues (low / high halves, each exact in float64), keeps a fixed sample
+    of a large batch and the whole of a small one, and stays under 64 MB at the headline shape."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = np.random.default_rng(5)
+    x = g.integers(0, 2**64, size=(5, 16), dtype=np.uint64)
+    x[0, :4] = [0, 1, bench.SOLINAS_P - 1, 2**64 - 1]
+    paths = bench.dump_outputs(str(tmp_path / "out"), "ntt_fwd_inv", x.view(np.int64))
+    assert [os.path.basename(p) for p in paths] == ["ntt_fwd_inv_lo32.npy", "ntt_fwd_inv_hi32.npy"]
+    lo, hi = (np.load(p) for p in paths)
+    assert lo.dtype == hi.dtype == np.float64 and lo.shape == hi.shape == x.shape
+    assert np.array_equal(lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32)), x)
+    rows = bench.dump_rows(bench.BATCH)
+    assert len(rows) == bench.DUMP_ROWS == len(set(rows.tolist())) and np.all(np.diff(rows) > 0)
+    assert 0 <= rows[0] and rows[-1] < bench.BATCH and np.array_equal(rows, bench.dump_rows(bench.BATCH))
+    assert np.array_equal(bench.dump_rows(64), np.arange(64))
+    assert 2 * bench.DUMP_ROWS * bench.N * 8 <= 64 * 10**6
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, oracle):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs the headline alone (no leg, no baseline, no record file),
+    reports K and ms_per_step, and --dump-outputs holds the batch as W + K fwd+inv steps leave it (the oracle's)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    K, W, batch = 3, 1, 64
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup",
+                          str(W), "--batch", str(batch), "--dump-outputs", str(tmp_path)],
+                         check=True, capture_output=True, text=True, timeout=120)
+    line = json.loads(res.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "forward+inverse NTTs/sec, N=2048 u64 prime, batch=8192"
+    assert line["unit"] == "fwd+inv NTT pairs/s" and line["higher_is_better"] is True and line["dtype"] == "u64"
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0
+    assert abs(line["value"] - batch / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["legs_summary"] == {} and line["cpu_baseline"] is None and line["full_record"] is None
+    assert "cold_start" not in line and "steady_state" not in line
+    want = oracle.fill_uniform(bench.SEED, bench.SOLINAS_P, batch * bench.N).reshape(batch, bench.N)
+    ref = oracle.Plan.try_new(bench.N, bench.SOLINAS_P)
+    for _ in range(W + K):
+        want = ref.inv(ref.fwd(want))
+    lo, hi = (np.load(tmp_path / f"ntt_fwd_inv_{h}32.npy") for h in ("lo", "hi"))
+    assert sorted(os.listdir(tmp_path)) == ["ntt_fwd_inv_hi32.npy", "ntt_fwd_inv_lo32.npy"]
+    assert lo.dtype == hi.dtype == np.float64
+    assert np.array_equal(lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32)), want)
 
 
 def _stub_leg(i, nested=False):

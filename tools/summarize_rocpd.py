@@ -62,7 +62,7 @@ def main():
             "achieved_GBps": ALG_BYTES / (avg * 1e-9) / 1e9, "frac": ALG_BYTES / (avg * 1e-9) / PEAK}
     out = {"source": os.path.basename(db), "headline_kernels": head}
     if line:
-        # bench.py's launch order for the transform at the headline grid: cold start (W warmup + K timed steps),
+        # bench.py --full's launch order for the transform at the headline grid: cold start (W warmup + K timed steps),
         # the legs (other kernels), the headline (W warmup + K timed steps), steady state, the direction split
         W, K = line["warmup"], line["steps"]
         # runs of consecutive dispatches alternating forward / inverse body at the headline grid (the split-transform

@@ -561,6 +561,49 @@ int mi_lwe_modulus_switch32_batch(uint64_t *switched, const uint32_t *lwe_in, si
 int mi_lwe_modulus_switch_batch(uint64_t *switched, const uint64_t *lwe_in, size_t lwe_dim, size_t batch,
                                 int log_modulus, int ms_mode, int device, void *stream);
 
+/* ---- LWE packing keyswitch and GLWE compression ---------------------------------------------------------------
+ * What shortint's CompressedCiphertextList is built on (COMP_PARAM_MESSAGE_2_CARRY_2: 2048 -> k = 4, N = 256,
+ * base 2^4, 3 levels, 256 LWEs per GLWE, storage log modulus 12; shortint/parameters/v1_4/list_compression/).
+ * mi_lwe_pksk_create takes the reference's LwePackingKeyswitchKey layout as a device pointer: in_dim blocks of `level`
+ * GLWE ciphertexts of (glwe_dim + 1) * polynomial_size u64, levels stored as generate_lwe_packing_keyswitch_key
+ * writes them (lwe_packing_keyswitch_key_generation.rs:129-156), and prepares a private device copy (the caller's
+ * buffer may be freed afterwards; the preparation runs on `stream` and synchronises it).  polynomial_size a power of
+ * two, (glwe_dim + 1) * polynomial_size < 2^24; MI_ERR_INVALID_ARG where SignedDecomposer::new asserts
+ * (base_log * level outside [1, 63]); MI_ERR_UNSUPPORTED beyond the 2^17 GEMM-depth bound of mi_lwe_ksk_create. */
+typedef struct mi_lwe_pksk mi_lwe_pksk;
+int mi_lwe_pksk_create(const uint64_t *pksk, size_t in_dim, int glwe_dim, size_t polynomial_size, int base_log,
+                       int level, int device, void *stream, mi_lwe_pksk **out_key);
+int mi_lwe_pksk_destroy(mi_lwe_pksk *key);
+int mi_lwe_pksk_info(const mi_lwe_pksk *key, size_t *in_dim, int *glwe_dim, size_t *polynomial_size, int *base_log,
+                     int *level);
+/* keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext (lwe_packing_keyswitch.rs:296-379) over a list of lists:
+ * n_lwe ciphertexts (in_dim + 1 u64 each), lwe_per_glwe <= polynomial_size per output GLWE;
+ * ceil(n_lwe / lwe_per_glwe) GLWEs of (glwe_dim + 1) * polynomial_size u64 are written, the last one holding the
+ * remainder (shortint's chunks(lwe_per_glwe)).  GLWE g = sum_d X^d * keyswitch_lwe_ciphertext_into_glwe_ciphertext(
+ * lwe_in[g * lwe_per_glwe + d]) (:102-187: the mask is rounded with closest_representable before it is decomposed),
+ * so lwe_per_glwe = 1 is that function over a batch.  Native 2^64 modulus, bit-exact.  Device pointers, async on
+ * `stream`; stream-ordered scratch of at most 64 MiB of keyswitched rows (or one row, if larger) plus their digits,
+ * freed before return: larger calls run in chunks.  n_lwe = 0 is MI_OK. */
+int mi_lwe_packing_keyswitch_batch(const mi_lwe_pksk *key, uint64_t *glwe_out, const uint64_t *lwe_in, size_t n_lwe,
+                                   size_t lwe_per_glwe, void *stream);
+/* The u64 words of one CompressedModulusSwitchedGlweCiphertext's PackedIntegers:
+ * ceil((glwe_dim * polynomial_size + bodies_count) * log_modulus / 64)
+ * (compressed_modulus_switched_glwe_ciphertext.rs:229-232).  bodies_count <= polynomial_size and
+ * 1 <= log_modulus <= 64, as compress asserts (:191-203); else MI_ERR_INVALID_ARG, here and below. */
+int mi_glwe_compressed_words(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus,
+                             size_t *words);
+/* CompressedModulusSwitchedGlweCiphertext::compress (:169-220) over a batch of native-modulus GLWEs: the first
+ * glwe_dim * polynomial_size + bodies_count words of glwe[b], each through modulus_switch (fft_impl/common.rs:10-23),
+ * packed log_modulus bits each, little end first, as PackedIntegers::pack does (entities/packed_integers.rs:39-130),
+ * into packed[b] (mi_glwe_compressed_words u64).  Device pointers, async on `stream`. */
+int mi_glwe_compress_batch(uint64_t *packed, const uint64_t *glwe, size_t polynomial_size, int glwe_dim,
+                           size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
+/* CompressedModulusSwitchedGlweCiphertext::extract (:226-256): glwe[b] ((glwe_dim + 1) * polynomial_size u64) = the
+ * unpacked values (PackedIntegers::unpack, packed_integers.rs:132-222) shifted left by 64 - log_modulus, then
+ * polynomial_size - bodies_count zeros. */
+int mi_glwe_extract_batch(uint64_t *glwe, const uint64_t *packed, size_t polynomial_size, int glwe_dim,
+                          size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@
 
 #include "ntt64_launch.hpp"
 #include "keyswitch_launch.hpp"
+#include "ks_device.hpp"
 
 namespace mi {
 namespace ks {
@@ -44,11 +45,13 @@ namespace ks {
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 using u64 = uint64_t;
 
-// decomposer.rs:64-71 + :156-185 init_decomposer_state (native u64, closest representable)
-__device__ __forceinline__ u64 decomp_init(u64 input, int base_log, int level) {
+// decomposer.rs:64-71 + :156-185 init_decomposer_state (native u64, closest representable).  pre_rounded: the
+// packing keyswitch decomposes closest_representable(input) (lwe_packing_keyswitch.rs:173-174), whose rounding bit
+// is 0, so the tie state 2^(rep-1) is balanced only when the bit below it is set; the state is otherwise the same.
+__device__ __forceinline__ u64 decomp_init(u64 input, int base_log, int level, bool pre_rounded = false) {
   const unsigned rep = (unsigned)(base_log * level), non_rep = 64u - rep;
   u64 res = input >> (non_rep - 1);
-  const u64 rounding_bit = res & 1u;
+  const u64 rounding_bit = pre_rounded ? 0u : res & 1u;
   res += 1;
   res >>= 1;
   res &= (~0ull) >> (64u - rep);
@@ -81,6 +84,8 @@ __device__ __forceinline__ int8_t signed_byte(u64 x, int t) {
 struct Shape {
   uint32_t in_dim, out_size, level, base_log, nd, K, KB, CT;
   uint32_t body_log;  // KS32 (keyswitch_lwe_ciphertext_with_scalar_change): the output modulus 2^body_log
+  uint32_t body_col;  // the output column that receives the input body: out_size - 1 (LWE), k N (packing)
+  uint32_t pre_rounded;  // packing keyswitch: digits of closest_representable(a_i) (decomp_init)
 };
 
 __device__ __forceinline__ uint4 pack16(const int8_t (&b)[16]) {
@@ -164,6 +169,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     int8_t b[16];
     const u64* x = lwe_in + (uint64_t)row * (s.in_dim + 1);
     const int bl = (int)s.base_log, lv = (int)s.level;
+    const bool pre = s.pre_rounded != 0;
     // digit column k = (i * level + li) * nd + sb, walked incrementally: 3 divisions per thread, not 3 per
     // digit; terms come least significant first (iter.rs:103-119)
     const uint32_t k0 = kb * 64 + 16 * g, kd0 = k0 / s.nd;
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     u64 state = 0;
     int d = 0;
     if (live && k0 < s.K) {  // the state after terms 0..li of coefficient i
-      state = decomp_init(x[i], bl, lv);
+      state = decomp_init(x[i], bl, lv, pre);
       for (uint32_t u = 0; u <= li; ++u) d = decompose_one(bl, state);
     }
     for (int j = 0; j < 16; ++j) {
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
         if (++li == s.level) {  // next mask coefficient
           li = 0;
           ++i;
-          if (on) state = decomp_init(x[i], bl, lv);
+          if (on) state = decomp_init(x[i], bl, lv, pre);
         }
         if (on) d = decompose_one(bl, state);
       }
@@ -222,7 +228,7 @@ __global__ __launch_bounds__(256) void ks_digits_l_kernel(uint4* __restrict__ af
     const uint32_t kbi = cw / CPB, c = cw % CPB;
     const uint32_t row = mg * GM * 16 + R, i = kb0 * CPB + cw;
     const u64 x = (row < batch && i < s.in_dim) ? lwe_in[(uint64_t)row * (s.in_dim + 1) + i] : 0;
-    u64 state = decomp_init(x, bl, LEVEL);  // 0 decomposes to 0 at every level (padding rows / columns)
+    u64 state = decomp_init(x, bl, LEVEL, s.pre_rounded != 0);  // 0 decomposes to 0 at every level (padding rows / columns)
     W w = 0;
 #pragma unroll
     for (int l = 0; l < LEVEL; ++l) w |= (W)(uint8_t)(int8_t)decompose_one(bl, state) << (8 * l);
@@ -388,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ks_gemm_kernel(void* __restrict__ 
   for (int c = 0; c < CW; ++c) {
     const uint32_t col = (cg * GN + wc * CW + c) * 16 + (lane & 15);
     if (col >= s.out_size) continue;
-    const bool is_body = col == s.out_size - 1;
+    const bool is_body = col == s.body_col;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -413,13 +419,6 @@ __global__ __launch_bounds__(64 * NW, 1) void ks_gemm_kernel(void* __restrict__ 
 // ---- the modulus switch of an LWE (lwe_ciphertext_modulus_switch / lwe_ciphertext_centered_binary_modulus_switch,
 // algorithms/modulus_switch.rs:14-104): u32 words for the KS32 bootstrap's input (mockups/tfhe-hpu-mockup/src/lib.rs:
 // 720-736), u64 words for the native-modulus ciphertexts of every other PBS ----
-// modulus_switch (fft_impl/common.rs:10-23) at Scalar = T: identity at log_mod == BITS
-template <typename T>
-__device__ __forceinline__ T ms_word(T x, uint32_t log_mod) {
-  constexpr uint32_t BITS = 8 * sizeof(T);
-  return log_mod >= BITS ? x : (T)(x + ((T)1 << (BITS - log_mod - 1u))) >> (BITS - log_mod);
-}
-
 // One wave per ciphertext: the switched mask (LazyStandardModulusSwitchedLweCiphertext::mask,
 // modulus_switched_lwe_ciphertext.rs:164-172) and, when `centered`, the body correction of
 // lwe_ciphertext_centered_binary_modulus_switch (modulus_switch.rs:56-102) at Scalar = T / Signed: the wrapping
@@ -474,30 +473,27 @@ __global__ __launch_bounds__(256) void lwe_ms_kernel(u64* __restrict__ out, cons
 
 int ks_digit_bytes_per_term(int base_log) { return (base_log + 1 + 7) / 8; }
 
-// k32: the KS32 key geometry (ks::Geo<true>)
-static ks::Shape ks_shape(size_t in_dim, size_t out_dim, int base_log, int level, bool k32 = false) {
+static ks::Shape ks_shape(const KsGeometry& g) {
+  const bool k32 = g.mode == KsMode::Ks32;
   const uint32_t gn = k32 ? ks::Geo<true>::GN : ks::Geo<false>::GN;
   ks::Shape s;
-  s.in_dim = (uint32_t)in_dim;
-  s.out_size = (uint32_t)(out_dim + 1);
-  s.level = (uint32_t)level;
-  s.base_log = (uint32_t)base_log;
-  s.nd = (uint32_t)ks_digit_bytes_per_term(base_log);
-  s.K = (uint32_t)(in_dim * (size_t)level * s.nd);
+  s.in_dim = (uint32_t)g.in_dim;
+  s.out_size = (uint32_t)g.out_size;
+  s.level = (uint32_t)g.level;
+  s.base_log = (uint32_t)g.base_log;
+  s.nd = (uint32_t)ks_digit_bytes_per_term(g.base_log);
+  s.K = (uint32_t)(g.in_dim * (size_t)g.level * s.nd);
   s.KB = (s.K + 63) / 64;
   s.CT = (s.out_size + 16 * gn - 1) / (16 * gn) * gn;  // whole column groups
-  s.body_log = 64;
+  s.body_log = k32 ? (uint32_t)g.out_log : 64;
+  s.body_col = (uint32_t)g.body_col;
+  s.pre_rounded = g.mode == KsMode::Packing;
   return s;
 }
 
-size_t ks_key_bytes(size_t in_dim, size_t out_dim, int base_log, int level) {
-  const ks::Shape s = ks_shape(in_dim, out_dim, base_log, level);
-  return (size_t)s.CT * s.KB * ks::Geo<false>::NPL * 64 * 16;
-}
-
-size_t ks32_key_bytes(size_t in_dim, size_t out_dim, int base_log, int level) {
-  const ks::Shape s = ks_shape(in_dim, out_dim, base_log, level, true);
-  return (size_t)s.CT * s.KB * ks::Geo<true>::NPL * 64 * 16;
+size_t ks_key_bytes(const KsGeometry& g) {
+  const ks::Shape s = ks_shape(g);
+  return (size_t)s.CT * s.KB * (g.mode == KsMode::Ks32 ? ks::Geo<true>::NPL : ks::Geo<false>::NPL) * 64 * 16;
 }
 
 size_t ks_digit_bytes(size_t in_dim, int base_log, int level, size_t batch) {
@@ -506,21 +502,17 @@ size_t ks_digit_bytes(size_t in_dim, int base_log, int level, size_t batch) {
   return rows * kb * 64;
 }
 
-hipError_t launch_ksk_prepare(void* frag, const uint64_t* ksk, size_t in_dim, size_t out_dim, int base_log, int level,
-                              hipStream_t st) {
-  const ks::Shape s = ks_shape(in_dim, out_dim, base_log, level);
-  const uint64_t total = (uint64_t)s.CT * s.KB * ks::Geo<false>::NPL * 64;
+hipError_t launch_ksk_prepare(void* frag, const void* ksk, const KsGeometry& g, hipStream_t st) {
+  const ks::Shape s = ks_shape(g);
+  const bool k32 = g.mode == KsMode::Ks32;
+  const uint64_t total = (uint64_t)s.CT * s.KB * (k32 ? ks::Geo<true>::NPL : ks::Geo<false>::NPL) * 64;
   const unsigned grid = (unsigned)((total + 255) / 256 < 65535 * 4 ? (total + 255) / 256 : 65535 * 4);
-  hipLaunchKernelGGL(ks::ksk_prepare_kernel<uint64_t>, dim3(grid), dim3(256), 0, st, (uint4*)frag, ksk, s);
-  return hipGetLastError();
-}
-
-hipError_t launch_ksk32_prepare(void* frag, const uint32_t* ksk, size_t in_dim, size_t out_dim, int base_log,
-                                int level, hipStream_t st) {
-  const ks::Shape s = ks_shape(in_dim, out_dim, base_log, level, true);
-  const uint64_t total = (uint64_t)s.CT * s.KB * ks::Geo<true>::NPL * 64;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 * 4 ? (total + 255) / 256 : 65535 * 4);
-  hipLaunchKernelGGL(ks::ksk_prepare_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (uint4*)frag, ksk, s);
+  if (k32)
+    hipLaunchKernelGGL(ks::ksk_prepare_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (uint4*)frag,
+                       (const uint32_t*)ksk, s);
+  else
+    hipLaunchKernelGGL(ks::ksk_prepare_kernel<uint64_t>, dim3(grid), dim3(256), 0, st, (uint4*)frag,
+                       (const uint64_t*)ksk, s);
   return hipGetLastError();
 }
 
@@ -542,12 +534,14 @@ hipError_t launch_lwe_ms64(uint64_t* out, const uint64_t* in, size_t dim, size_t
   return hipGetLastError();
 }
 
-// out_log 0: the native u64 keyswitch into `out` (u64); else KS32 into u32 words with output modulus 2^out_log
-static hipError_t keyswitch_launch(void* out, const uint64_t* lwe_in, const void* frag, void* digits, size_t batch,
-                                   size_t in_dim, size_t out_dim, int base_log, int level, int out_log, hipStream_t st) {
+// Digits, then the GEMM, of `batch` ciphertexts; the key object's geometry says which of the three keyswitches this
+// is (nothing is inferred from the parameters): u64 rows of out_size words (Native, Packing) or u32 rows (Ks32).
+hipError_t launch_keyswitch(void* out, const uint64_t* lwe_in, const void* frag, void* digits, size_t batch,
+                            const KsGeometry& g, hipStream_t st) {
   if (batch == 0) return hipSuccess;
-  ks::Shape s = ks_shape(in_dim, out_dim, base_log, level, out_log != 0);
-  if (out_log) s.body_log = (uint32_t)out_log;
+  const ks::Shape s = ks_shape(g);
+  const bool k32 = g.mode == KsMode::Ks32;
+  const int level = g.level;
   const uint32_t rows = (uint32_t)((batch + 16 * ks::GM - 1) / (16 * ks::GM) * 16 * ks::GM);
   const uint64_t total = (uint64_t)rows * s.KB * 4;
   const unsigned dgrid = (unsigned)((total + 255) / 256 < 65535 * 4 ? (total + 255) / 256 : 65535 * 4);
@@ -564,26 +558,16 @@ static hipError_t keyswitch_launch(void* out, const uint64_t* lwe_in, const void
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const uint32_t n_mg = rows / (16 * ks::GM), n_cg = s.CT / (out_log ? ks::Geo<true>::GN : ks::Geo<false>::GN);
+  const uint32_t n_mg = rows / (16 * ks::GM), n_cg = s.CT / (k32 ? ks::Geo<true>::GN : ks::Geo<false>::GN);
   const uint32_t tiles = (n_mg + 7) / 8 * 8 * n_cg;
   const unsigned grid = 8 * ((tiles + 7) / 8);
-  if (out_log)
+  if (k32)
     hipLaunchKernelGGL(ks::ks_gemm_kernel<true>, dim3(grid), dim3(64 * ks::NW), 0, st, out, lwe_in, (const uint4*)digits,
                        (const uint4*)frag, (uint32_t)batch, n_mg, s);
   else
     hipLaunchKernelGGL(ks::ks_gemm_kernel<false>, dim3(grid), dim3(64 * ks::NW), 0, st, out, lwe_in, (const uint4*)digits,
                        (const uint4*)frag, (uint32_t)batch, n_mg, s);
   return hipGetLastError();
-}
-
-hipError_t launch_keyswitch(uint64_t* out, const uint64_t* lwe_in, const void* frag, void* digits, size_t batch,
-                            size_t in_dim, size_t out_dim, int base_log, int level, hipStream_t st) {
-  return keyswitch_launch(out, lwe_in, frag, digits, batch, in_dim, out_dim, base_log, level, 0, st);
-}
-
-hipError_t launch_keyswitch32(uint32_t* out, const uint64_t* lwe_in, const void* frag, void* digits, size_t batch,
-                              size_t in_dim, size_t out_dim, int base_log, int level, int out_log, hipStream_t st) {
-  return keyswitch_launch(out, lwe_in, frag, digits, batch, in_dim, out_dim, base_log, level, out_log, st);
 }
 
 }  // namespace mi

@@ -147,6 +147,14 @@ _SIGS = {
     "mi_lwe_keyswitch32_batch": (_int, [_vp, _vp, _vp, _sz, _vp]),
     "mi_lwe_modulus_switch32_batch": (_int, [_vp, _vp, _sz, _sz, _int, _int, _int, _vp]),
     "mi_lwe_modulus_switch_batch": (_int, [_vp, _vp, _sz, _sz, _int, _int, _int, _vp]),
+    "mi_lwe_pksk_create": (_int, [_vp, _sz, _int, _sz, _int, _int, _int, _vp, ctypes.POINTER(_vp)]),
+    "mi_lwe_pksk_destroy": (_int, [_vp]),
+    "mi_lwe_pksk_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_sz),
+                                ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "mi_lwe_packing_keyswitch_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "mi_glwe_compressed_words": (_int, [_sz, _int, _sz, _int, ctypes.POINTER(_sz)]),
+    "mi_glwe_compress_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
+    "mi_glwe_extract_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
 }
 
 

@@ -103,6 +103,27 @@ def test_ks32_errors(engine):
                                                        torch.zeros((3, 5), dtype=torch.int32, device="cuda"))
 
 
+def test_ksk_info_reports_the_key_shape(engine):
+    """`mi_lwe_ksk_info` / `mi_lwe_ksk32_info` answer what the key was created with, all at once and one out pointer
+    at a time (every other one NULL)."""
+    import ctypes
+    import torch
+    KS, L = engine.lwe_keyswitch, engine._lib.lib()
+    sz, ci = ctypes.c_size_t, ctypes.c_int
+    native = KS.LweKeyswitchKey(torch.zeros((8, 4, 11), dtype=torch.int64, device="cuda"), 4, 4)
+    ks32 = KS.LweKeyswitchKey32(torch.zeros((8, 8, 11), dtype=torch.int32, device="cuda"), 2, 8, 21)
+    for info, key, types, want in ((L.mi_lwe_ksk_info, native, (sz, sz, ci, ci), (8, 10, 4, 4)),
+                                   (L.mi_lwe_ksk32_info, ks32, (sz, sz, ci, ci, ci), (8, 10, 2, 8, 21))):
+        outs = [t(99) for t in types]
+        assert info(key._h, *[ctypes.byref(o) for o in outs]) == engine._lib.MI_OK
+        assert tuple(o.value for o in outs) == want
+        for i, t in enumerate(types):
+            outs = [t(99) for t in types]
+            args = [ctypes.byref(o) if j == i else None for j, o in enumerate(outs)]
+            assert info(key._h, *args) == engine._lib.MI_OK
+            assert [o.value for o in outs] == [want[j] if j == i else 99 for j in range(len(types))]
+
+
 @pytest.mark.parametrize("lut_nb", [1, 2])
 def test_ks32_bootstrap_hpu_flow(engine, oracle, lut_nb):
     """The HPU KS32 bootstrap end to end under real keys at V1_5_HPU_PARAM_MESSAGE_2_CARRY_2_KS32_PBS_TUNIFORM_2M128:

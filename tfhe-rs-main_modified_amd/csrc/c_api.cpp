@@ -2,7 +2,9 @@
 //
 // Owns plan construction (host twiddles exactly as tfhe-ntt/src/prime64.rs:159-204 + 764-862,
 // uploaded once to the plan's device) and argument validation; never aborts, every failure is
-// a status code plus a thread-local message.
+// a status code plus a thread-local message.  The f64-FFT path, the serialised keys, the keyswitch family and
+// the multi-GPU helpers have their own files (c_api_fft.cpp, c_api_keys.cpp, c_api_keyswitch.cpp,
+// c_api_multi_gpu.cpp).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -20,7 +22,6 @@
 
 #include "scratch.hpp"
 #include "build_info.hpp"  // build/ (Makefile): MI_SOURCE_HASH
-#include "keyswitch_launch.hpp"
 #include "c_api_internal.hpp"
 #include "mi_arith.hpp"
 #include "ntt64_tw_tables.hpp"
@@ -1306,396 +1307,6 @@ int mi_native_polymul_batch(const mi_native_plan* plan, void* prod, const void* 
   }
   (void)mi::scratch_free(scratch, s);
   return st;
-}
-
-// ---- LWE keyswitch (tfhe/src/core_crypto/algorithms/lwe_keyswitch.rs:137-227) -----------------------
-
-struct mi_lwe_ksk {
-  int device = 0;
-  size_t in_dim = 0, out_dim = 0;
-  int base_log = 0, level = 0;
-  mi::KsGeometry geo;    // what the launches are told (KsMode::Native)
-  void* frag = nullptr;  // byte-plane MFMA fragments (keyswitch.hip)
-};
-
-int mi_lwe_ksk_create(const uint64_t* ksk, size_t in_dim, size_t out_dim, int base_log, int level, int device,
-                      void* stream, mi_lwe_ksk** out_key) {
-  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
-  *out_key = nullptr;
-  if (!ksk) return fail(MI_ERR_INVALID_ARG, "ksk is NULL");
-  if (in_dim == 0 || out_dim == 0 || in_dim > 0xFFFFFFull || out_dim > 0xFFFFFFull)
-    return fail(MI_ERR_INVALID_ARG, "lwe dimension out of range");
-  // SignedDecomposer::new (decomposer.rs): base_log * level < 64, both >= 1
-  if (base_log < 1 || level < 1 || base_log * level >= 64)
-    return fail(MI_ERR_INVALID_ARG, "decomposition base_log * level must be in [1, 63]");
-  // exact int32 accumulation on the int8 matrix cores: GEMM depth in_dim * level * bytes-per-digit < 2^17
-  if ((double)in_dim * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
-    return fail(MI_ERR_UNSUPPORTED, "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
-  mi_lwe_ksk* key = new (std::nothrow) mi_lwe_ksk;
-  if (!key) return fail(MI_ERR_OOM, "host allocation failed");
-  key->device = device;
-  key->in_dim = in_dim;
-  key->out_dim = out_dim;
-  key->base_log = base_log;
-  key->level = level;
-  key->geo.mode = mi::KsMode::Native;
-  key->geo.in_dim = in_dim;
-  key->geo.out_size = out_dim + 1;
-  key->geo.base_log = base_log;
-  key->geo.level = level;
-  key->geo.body_col = out_dim;
-  DeviceGuard g(device);
-  if (!g.ok) {
-    delete key;
-    return fail(MI_ERR_INVALID_ARG, "bad device");
-  }
-  if (hipMalloc(&key->frag, mi::ks_key_bytes(key->geo)) != hipSuccess) {
-    delete key;
-    return fail(MI_ERR_OOM, "keyswitch key allocation failed");
-  }
-  // ordered after the work that produced `ksk` on the caller's stream
-  hipError_t e = mi::launch_ksk_prepare(key->frag, ksk, key->geo, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess) {
-    (void)hipFree(key->frag);
-    delete key;
-    return hip_fail(e, "keyswitch key preparation");
-  }
-  *out_key = key;
-  return MI_OK;
-}
-
-int mi_lwe_ksk_destroy(mi_lwe_ksk* key) {
-  if (!key) return MI_OK;
-  {
-    DeviceGuard g(key->device);
-    if (key->frag) (void)hipFree(key->frag);
-  }
-  delete key;
-  return MI_OK;
-}
-
-int mi_lwe_ksk_info(const mi_lwe_ksk* key, size_t* in_dim, size_t* out_dim, int* base_log, int* level) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (in_dim) *in_dim = key->in_dim;
-  if (out_dim) *out_dim = key->out_dim;
-  if (base_log) *base_log = key->base_log;
-  if (level) *level = key->level;
-  return MI_OK;
-}
-
-int mi_lwe_keyswitch_batch(const mi_lwe_ksk* key, uint64_t* lwe_out, const uint64_t* lwe_in, size_t batch,
-                           void* stream) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (batch == 0) return MI_OK;
-  if (!lwe_out || !lwe_in) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (batch > 0x3FFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  const hipStream_t s = (hipStream_t)stream;
-  DeviceGuard g(key->device);
-  void* digits = nullptr;  // int8 digit fragments, stream-ordered scratch
-  if (mi::scratch_alloc((void**)&digits, mi::ks_digit_bytes(key->in_dim, key->base_log, key->level, batch), s) != hipSuccess)
-    return fail(MI_ERR_OOM, "scratch allocation failed");
-  hipError_t e = mi::launch_keyswitch(lwe_out, lwe_in, key->frag, digits, batch, key->geo, s);
-  (void)mi::scratch_free(digits, s);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "keyswitch launch");
-}
-
-// ---- KS32: keyswitch_lwe_ciphertext_with_scalar_change (lwe_keyswitch.rs:331-447) ------------------------------
-// The keyswitch of the HPU KS32 parameter sets (shortint/parameters/v1_5/hpu.rs:57-76: 2048 -> 879, base 2^2, 8
-// levels, post_keyswitch_ciphertext_modulus 2^21): u64 input LWEs of the native modulus, u32 key and output words
-// with the power-of-two output modulus 2^out_modulus_log encoded in the MSBs, as the reference stores it.
-
-struct mi_lwe_ksk32 {
-  int device = 0;
-  size_t in_dim = 0, out_dim = 0;
-  int base_log = 0, level = 0, out_modulus_log = 32;
-  mi::KsGeometry geo;  // KsMode::Ks32
-  void* frag = nullptr;  // byte-plane MFMA fragments of the zero-extended u32 key words (keyswitch.hip)
-};
-
-int mi_lwe_ksk32_create(const uint32_t* ksk, size_t in_dim, size_t out_dim, int base_log, int level,
-                        int out_modulus_log, int device, void* stream, mi_lwe_ksk32** out_key) {
-  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
-  *out_key = nullptr;
-  if (!ksk) return fail(MI_ERR_INVALID_ARG, "ksk is NULL");
-  if (in_dim == 0 || out_dim == 0 || in_dim > 0xFFFFFFull || out_dim > 0xFFFFFFull)
-    return fail(MI_ERR_INVALID_ARG, "lwe dimension out of range");
-  if (out_modulus_log < 1 || out_modulus_log > 32)
-    return fail(MI_ERR_INVALID_ARG, "output modulus must be 2^w with 1 <= w <= 32");
-  // lwe_keyswitch.rs:378-384: base_log * level <= OutputScalar::BITS (and SignedDecomposer::new's >= 1 each)
-  if (base_log < 1 || level < 1 || base_log * level > 32)
-    return fail(MI_ERR_INVALID_ARG, "decomposition base_log * level must be in [1, 32]");
-  if ((double)in_dim * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
-    return fail(MI_ERR_UNSUPPORTED, "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
-  mi_lwe_ksk32* key = new (std::nothrow) mi_lwe_ksk32;
-  if (!key) return fail(MI_ERR_OOM, "host allocation failed");
-  key->device = device;
-  key->in_dim = in_dim;
-  key->out_dim = out_dim;
-  key->base_log = base_log;
-  key->level = level;
-  key->out_modulus_log = out_modulus_log;
-  key->geo.mode = mi::KsMode::Ks32;
-  key->geo.in_dim = in_dim;
-  key->geo.out_size = out_dim + 1;
-  key->geo.base_log = base_log;
-  key->geo.level = level;
-  key->geo.out_log = out_modulus_log;
-  key->geo.body_col = out_dim;
-  DeviceGuard g(device);
-  if (!g.ok) {
-    delete key;
-    return fail(MI_ERR_INVALID_ARG, "bad device");
-  }
-  if (hipMalloc(&key->frag, mi::ks_key_bytes(key->geo)) != hipSuccess) {
-    delete key;
-    return fail(MI_ERR_OOM, "keyswitch key allocation failed");
-  }
-  hipError_t e = mi::launch_ksk_prepare(key->frag, ksk, key->geo, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess) {
-    (void)hipFree(key->frag);
-    delete key;
-    return hip_fail(e, "keyswitch key preparation");
-  }
-  *out_key = key;
-  return MI_OK;
-}
-
-int mi_lwe_ksk32_destroy(mi_lwe_ksk32* key) {
-  if (!key) return MI_OK;
-  {
-    DeviceGuard g(key->device);
-    if (key->frag) (void)hipFree(key->frag);
-  }
-  delete key;
-  return MI_OK;
-}
-
-int mi_lwe_ksk32_info(const mi_lwe_ksk32* key, size_t* in_dim, size_t* out_dim, int* base_log, int* level,
-                      int* out_modulus_log) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (in_dim) *in_dim = key->in_dim;
-  if (out_dim) *out_dim = key->out_dim;
-  if (base_log) *base_log = key->base_log;
-  if (level) *level = key->level;
-  if (out_modulus_log) *out_modulus_log = key->out_modulus_log;
-  return MI_OK;
-}
-
-int mi_lwe_keyswitch32_batch(const mi_lwe_ksk32* key, uint32_t* lwe_out, const uint64_t* lwe_in, size_t batch,
-                             void* stream) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (batch == 0) return MI_OK;
-  if (!lwe_out || !lwe_in) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (batch > 0x3FFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  const hipStream_t s = (hipStream_t)stream;
-  DeviceGuard g(key->device);
-  void* digits = nullptr;
-  if (mi::scratch_alloc((void**)&digits, mi::ks_digit_bytes(key->in_dim, key->base_log, key->level, batch), s) != hipSuccess)
-    return fail(MI_ERR_OOM, "scratch allocation failed");
-  hipError_t e = mi::launch_keyswitch(lwe_out, lwe_in, key->frag, digits, batch, key->geo, s);
-  (void)mi::scratch_free(digits, s);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "keyswitch launch");
-}
-
-// shared checks of the two LWE modulus switches: the standard switch is defined for 1 <= log_modulus <= BITS (identity at
-// BITS, fft_impl/common.rs:10-23); the centered one computes 1 << (BITS - log_modulus - 1) (modulus_switch.rs:95), so
-// it needs log_modulus < BITS (the reference's shift underflows there)
-static int check_lwe_ms(const void* switched, const void* lwe_in, size_t lwe_dim, size_t batch, int log_modulus,
-                        int ms_mode, int bits) {
-  if (!switched || !lwe_in) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (lwe_dim == 0 || lwe_dim > 0xFFFFFFull || batch > 0xFFFFFFFFull)
-    return fail(MI_ERR_INVALID_ARG, "lwe dimension or batch out of range");
-  if (ms_mode != MI_MS_STANDARD && ms_mode != MI_MS_CENTERED)
-    return fail(MI_ERR_INVALID_ARG, "ms_mode must be MI_MS_STANDARD or MI_MS_CENTERED");
-  const int top = ms_mode == MI_MS_CENTERED ? bits - 1 : bits;
-  if (log_modulus < 1 || log_modulus > top)
-    return fail(MI_ERR_INVALID_ARG, "log_modulus must be in [1, " + std::to_string(top) + "] for this ms_mode");
-  return MI_OK;
-}
-
-int mi_lwe_modulus_switch32_batch(uint64_t* switched, const uint32_t* lwe_in, size_t lwe_dim, size_t batch,
-                                  int log_modulus, int ms_mode, int device, void* stream) {
-  if (batch == 0) return MI_OK;
-  int st = check_lwe_ms(switched, lwe_in, lwe_dim, batch, log_modulus, ms_mode, 32);
-  if (st != MI_OK) return st;
-  DeviceGuard g(device);
-  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  hipError_t e = mi::launch_lwe_ms32(switched, lwe_in, lwe_dim, batch, log_modulus, ms_mode == MI_MS_CENTERED,
-                                     (hipStream_t)stream);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "modulus switch launch");
-}
-
-int mi_lwe_modulus_switch_batch(uint64_t* switched, const uint64_t* lwe_in, size_t lwe_dim, size_t batch,
-                                int log_modulus, int ms_mode, int device, void* stream) {
-  if (batch == 0) return MI_OK;
-  int st = check_lwe_ms(switched, lwe_in, lwe_dim, batch, log_modulus, ms_mode, 64);
-  if (st != MI_OK) return st;
-  DeviceGuard g(device);
-  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  hipError_t e = mi::launch_lwe_ms64(switched, lwe_in, lwe_dim, batch, log_modulus, ms_mode == MI_MS_CENTERED,
-                                     (hipStream_t)stream);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "modulus switch launch");
-}
-
-// ---- LWE packing keyswitch (tfhe/src/core_crypto/algorithms/lwe_packing_keyswitch.rs:102-187, 296-379) ----------
-
-struct mi_lwe_pksk {
-  int device = 0;
-  size_t in_dim = 0, polynomial_size = 0;
-  int glwe_dim = 0, base_log = 0, level = 0;
-  mi::KsGeometry geo;    // KsMode::Packing: (k + 1) N key columns, the body at column k N
-  void* frag = nullptr;  // byte-plane MFMA fragments (keyswitch.hip)
-};
-
-int mi_lwe_pksk_create(const uint64_t* pksk, size_t in_dim, int glwe_dim, size_t polynomial_size, int base_log,
-                       int level, int device, void* stream, mi_lwe_pksk** out_key) {
-  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
-  *out_key = nullptr;
-  if (!pksk) return fail(MI_ERR_INVALID_ARG, "pksk is NULL");
-  if (in_dim == 0 || in_dim > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "lwe dimension out of range");
-  if (polynomial_size == 0 || (polynomial_size & (polynomial_size - 1)) != 0)
-    return fail(MI_ERR_INVALID_ARG, "polynomial size must be a power of two");
-  if (glwe_dim < 1 || polynomial_size > 0xFFFFFFull || ((size_t)glwe_dim + 1) * polynomial_size > 0xFFFFFFull)
-    return fail(MI_ERR_INVALID_ARG, "glwe size out of range");
-  // SignedDecomposer::new (decomposer.rs): base_log * level < 64, both >= 1
-  if (base_log < 1 || level < 1 || base_log * level >= 64)
-    return fail(MI_ERR_INVALID_ARG, "decomposition base_log * level must be in [1, 63]");
-  // exact int32 accumulation on the int8 matrix cores: GEMM depth in_dim * level * bytes-per-digit < 2^17
-  if ((double)in_dim * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
-    return fail(MI_ERR_UNSUPPORTED, "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
-  mi_lwe_pksk* key = new (std::nothrow) mi_lwe_pksk;
-  if (!key) return fail(MI_ERR_OOM, "host allocation failed");
-  key->device = device;
-  key->in_dim = in_dim;
-  key->glwe_dim = glwe_dim;
-  key->polynomial_size = polynomial_size;
-  key->base_log = base_log;
-  key->level = level;
-  key->geo.mode = mi::KsMode::Packing;
-  key->geo.in_dim = in_dim;
-  key->geo.out_size = ((size_t)glwe_dim + 1) * polynomial_size;
-  key->geo.base_log = base_log;
-  key->geo.level = level;
-  key->geo.body_col = (size_t)glwe_dim * polynomial_size;
-  DeviceGuard g(device);
-  if (!g.ok) {
-    delete key;
-    return fail(MI_ERR_INVALID_ARG, "bad device");
-  }
-  if (hipMalloc(&key->frag, mi::ks_key_bytes(key->geo)) != hipSuccess) {
-    delete key;
-    return fail(MI_ERR_OOM, "packing keyswitch key allocation failed");
-  }
-  // ordered after the work that produced `pksk` on the caller's stream
-  hipError_t e = mi::launch_ksk_prepare(key->frag, pksk, key->geo, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess) {
-    (void)hipFree(key->frag);
-    delete key;
-    return hip_fail(e, "packing keyswitch key preparation");
-  }
-  *out_key = key;
-  return MI_OK;
-}
-
-int mi_lwe_pksk_destroy(mi_lwe_pksk* key) {
-  if (!key) return MI_OK;
-  {
-    DeviceGuard g(key->device);
-    if (key->frag) (void)hipFree(key->frag);
-  }
-  delete key;
-  return MI_OK;
-}
-
-int mi_lwe_pksk_info(const mi_lwe_pksk* key, size_t* in_dim, int* glwe_dim, size_t* polynomial_size, int* base_log,
-                     int* level) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (in_dim) *in_dim = key->in_dim;
-  if (glwe_dim) *glwe_dim = key->glwe_dim;
-  if (polynomial_size) *polynomial_size = key->polynomial_size;
-  if (base_log) *base_log = key->base_log;
-  if (level) *level = key->level;
-  return MI_OK;
-}
-
-int mi_lwe_packing_keyswitch_batch(const mi_lwe_pksk* key, uint64_t* glwe_out, const uint64_t* lwe_in, size_t n_lwe,
-                                   size_t lwe_per_glwe, void* stream) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  // lwe_packing_keyswitch.rs:358-360: lwe_ciphertext_count <= polynomial_size
-  if (lwe_per_glwe == 0 || lwe_per_glwe > key->polynomial_size)
-    return fail(MI_ERR_INVALID_ARG, "lwe_per_glwe must be in [1, polynomial_size]");
-  if (n_lwe == 0) return MI_OK;
-  if (!glwe_out || !lwe_in) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (n_lwe > 0xFFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  const hipStream_t s = (hipStream_t)stream;
-  DeviceGuard g(key->device);
-  const mi::PksPlan plan = mi::pks_plan(key->geo, n_lwe, lwe_per_glwe);
-  // stream-ordered scratch: the GEMM's rows, its int8 digit fragments, the rotate-and-sum pass's partial sums
-  void *t = nullptr, *digits = nullptr, *partials = nullptr;
-  bool ok = mi::scratch_alloc(&t, plan.t_bytes, s) == hipSuccess &&
-            mi::scratch_alloc(&digits, plan.digit_bytes, s) == hipSuccess &&
-            (plan.partial_bytes == 0 || mi::scratch_alloc(&partials, plan.partial_bytes, s) == hipSuccess);
-  hipError_t e = hipSuccess;
-  if (ok)
-    e = mi::launch_packing_keyswitch(glwe_out, lwe_in, key->frag, t, digits, partials, n_lwe, lwe_per_glwe,
-                                     key->polynomial_size, key->geo, plan, s);
-  if (partials) (void)mi::scratch_free(partials, s);
-  if (digits) (void)mi::scratch_free(digits, s);
-  if (t) (void)mi::scratch_free(t, s);
-  if (!ok) return fail(MI_ERR_OOM, "scratch allocation failed");
-  return e == hipSuccess ? MI_OK : hip_fail(e, "packing keyswitch launch");
-}
-
-// ---- CompressedModulusSwitchedGlweCiphertext (entities/compressed_modulus_switched_glwe_ciphertext.rs:169-256) ---
-
-// compress's asserts (:191-203) and PackedIntegers::pack's (packed_integers.rs:43-44)
-static int check_glwe_compress(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus) {
-  if (polynomial_size == 0 || glwe_dim < 1 || polynomial_size > 0xFFFFFFull ||
-      ((size_t)glwe_dim + 1) * polynomial_size > 0xFFFFFFull)
-    return fail(MI_ERR_INVALID_ARG, "glwe size out of range");
-  if (bodies_count > polynomial_size) return fail(MI_ERR_INVALID_ARG, "bodies_count must be <= polynomial_size");
-  if (log_modulus < 1 || log_modulus > 64) return fail(MI_ERR_INVALID_ARG, "log_modulus must be in [1, 64]");
-  return MI_OK;
-}
-
-int mi_glwe_compressed_words(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus,
-                             size_t* words) {
-  if (!words) return fail(MI_ERR_INVALID_ARG, "words is NULL");
-  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus);
-  if (st != MI_OK) return st;
-  *words = mi::glwe_compressed_words(polynomial_size, glwe_dim, bodies_count, log_modulus);
-  return MI_OK;
-}
-
-int mi_glwe_compress_batch(uint64_t* packed, const uint64_t* glwe, size_t polynomial_size, int glwe_dim,
-                           size_t bodies_count, int log_modulus, size_t batch, int device, void* stream) {
-  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus);
-  if (st != MI_OK) return st;
-  if (batch == 0) return MI_OK;
-  if (!packed || !glwe) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (batch > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  DeviceGuard g(device);
-  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  const hipError_t e = mi::launch_glwe_compress(packed, glwe, polynomial_size, glwe_dim, bodies_count, log_modulus,
-                                                batch, (hipStream_t)stream);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "glwe compression launch");
-}
-
-int mi_glwe_extract_batch(uint64_t* glwe, const uint64_t* packed, size_t polynomial_size, int glwe_dim,
-                          size_t bodies_count, int log_modulus, size_t batch, int device, void* stream) {
-  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus);
-  if (st != MI_OK) return st;
-  if (batch == 0) return MI_OK;
-  if (!packed || !glwe) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  if (batch > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  DeviceGuard g(device);
-  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  const hipError_t e = mi::launch_glwe_extract(glwe, packed, polynomial_size, glwe_dim, bodies_count, log_modulus,
-                                               batch, (hipStream_t)stream);
-  return e == hipSuccess ? MI_OK : hip_fail(e, "glwe extraction launch");
 }
 
 }  // extern "C"

@@ -496,8 +496,8 @@ size_t ks_key_bytes(const KsGeometry& g) {
   return (size_t)s.CT * s.KB * (g.mode == KsMode::Ks32 ? ks::Geo<true>::NPL : ks::Geo<false>::NPL) * 64 * 16;
 }
 
-size_t ks_digit_bytes(size_t in_dim, int base_log, int level, size_t batch) {
-  const size_t kb = (in_dim * (size_t)level * (size_t)ks_digit_bytes_per_term(base_log) + 63) / 64;
+size_t ks_digit_bytes(const KsGeometry& g, size_t batch) {
+  const size_t kb = (g.in_dim * (size_t)g.level * (size_t)ks_digit_bytes_per_term(g.base_log) + 63) / 64;
   const size_t rows = (batch + 16 * ks::GM - 1) / (16 * ks::GM) * 16 * ks::GM;
   return rows * kb * 64;
 }

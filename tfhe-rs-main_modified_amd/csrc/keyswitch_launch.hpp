@@ -27,7 +27,7 @@ struct KsGeometry {
 // keyswitch.hip — the keyswitches on the int8 matrix cores.
 size_t ks_key_bytes(const KsGeometry& g);   // the prepared key (byte-plane MFMA fragments)
 int ks_digit_bytes_per_term(int base_log);  // signed bytes per decomposition digit
-size_t ks_digit_bytes(size_t in_dim, int base_log, int level, size_t batch);
+size_t ks_digit_bytes(const KsGeometry& g, size_t batch);  // the digit fragments of `batch` input rows
 // ksk: u64 words (Native, Packing) or u32 words (Ks32) in the reference layout
 hipError_t launch_ksk_prepare(void* frag, const void* ksk, const KsGeometry& g, hipStream_t s);
 // out: batch rows of out_size u64 (Native, Packing) or u32 (Ks32) words

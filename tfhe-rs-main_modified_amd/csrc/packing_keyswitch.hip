@@ -145,7 +145,7 @@ PksPlan pks_plan(const KsGeometry& g, size_t n_lwe, size_t lwe_per_glwe) {
   const size_t dl = (per + part - 1) / part;
   p.part = (per + dl - 1) / dl;
   p.t_bytes = p.rows * row_bytes;
-  p.digit_bytes = ks_digit_bytes(g.in_dim, g.base_log, g.level, p.rows);
+  p.digit_bytes = ks_digit_bytes(g, p.rows);
   p.partial_bytes = p.part > 1 ? n_g * p.part * row_bytes : 0;
   return p;
 }

@@ -29,6 +29,25 @@ void scratch_stream_retired(hipStream_t s);
 // bytes held by the pool on `device` (idle + in use)
 size_t scratch_bytes(int device);
 
+// one scratch block for the length of a scope: freed on the stream it was taken on
+class ScratchBuf {
+ public:
+  explicit ScratchBuf(hipStream_t s) : s_(s) {}
+  ScratchBuf(size_t bytes, hipStream_t s) : s_(s) { (void)alloc(bytes); }
+  ScratchBuf(const ScratchBuf&) = delete;
+  ScratchBuf& operator=(const ScratchBuf&) = delete;
+  ~ScratchBuf() {
+    if (p_) (void)scratch_free(p_, s_);
+  }
+  bool alloc(size_t bytes) { return scratch_alloc(&p_, bytes, s_) == hipSuccess; }  // once per guard
+  void* ptr() const { return p_; }
+  bool ok() const { return p_ != nullptr; }
+
+ private:
+  void* p_ = nullptr;
+  hipStream_t s_;
+};
+
 // Pooled non-blocking side streams of the current device, for an entry point that splits its batch over the caller's
 // stream and up to MAX_SIDE more (pbs_large.hip, fft64_generic.hip): fork() orders each side stream after the work
 // already queued on the caller's stream, join() orders the caller's stream after everything queued on the side

@@ -241,6 +241,18 @@ def check(status: int) -> None:
         raise MiError(status, f"{text}: {detail}" if detail else text)
 
 
+def release(obj, destroy_name: str) -> None:
+    """The ``__del__`` of every class that owns a C handle in ``_h``: destroy it once, quietly (the object may be
+    half built, the interpreter may be shutting down)."""
+    h = getattr(obj, "_h", None)
+    if h:
+        try:
+            getattr(lib(), destroy_name)(h)
+        except Exception:
+            pass
+        obj._h = None
+
+
 def declared_symbols(header: str = HEADER_PATH) -> list[str]:
     """Every function the public header declares (used by the ABI export test)."""
     src = open(header).read()

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import check, lib
+from ._lib import check, lib, release
 from .ntt64_pbs import MS_CENTERED, MS_PRE_SWITCHED, MS_STANDARD, _dev, _stream  # noqa: F401
 
 
@@ -157,13 +157,7 @@ class FourierLweBootstrapKey:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_fft64_pbs_key_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_fft64_pbs_key_destroy")
 
     def output_lwe_size(self) -> int:
         return self.glwe_dimension * self.polynomial_size + 1

@@ -18,8 +18,33 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import check, lib
-from .ntt64_pbs import _dev, _stream
+from ._lib import check, lib, release
+from .ntt64_pbs import _dev, _dev32, _stream
+
+
+def _key_fields(key, ksk, base_log: int, level: int) -> None:
+    """The shape check and the fields the two key classes share."""
+    if ksk.dim() != 3 or ksk.shape[1] != level:
+        raise ValueError(f"assertion failed: ksk shape {tuple(ksk.shape)} != (in_dim, {level}, out_dim + 1)")
+    key.input_key_lwe_dimension = int(ksk.shape[0])
+    key.output_key_lwe_dimension = int(ksk.shape[2]) - 1
+    key.decomposition_base_log, key.decomposition_level_count = base_log, level
+    key.device = ksk.device
+
+
+def _check_lwe_batch(k, inp, out) -> int:
+    """The batch size of a keyswitch call, after the reference's dimension asserts."""
+    n_in, n_out = k.input_key_lwe_dimension + 1, k.output_key_lwe_dimension + 1
+    if inp.shape[-1] != n_in:
+        raise ValueError(f"assertion failed: Mismatched input LweDimension {inp.shape[-1] - 1} "
+                         f"!= {k.input_key_lwe_dimension}")
+    if out.shape[-1] != n_out:
+        raise ValueError(f"assertion failed: Mismatched output LweDimension {out.shape[-1] - 1} "
+                         f"!= {k.output_key_lwe_dimension}")
+    batch = inp.numel() // n_in
+    if out.numel() // n_out != batch:
+        raise ValueError("assertion failed: input and output batch sizes differ")
+    return batch
 
 
 class LweKeyswitchKey:
@@ -30,12 +55,7 @@ class LweKeyswitchKey:
     matrix-core copy is made; ``ksk`` may be released afterwards."""
 
     def __init__(self, ksk, base_log: int, level: int):
-        if ksk.dim() != 3 or ksk.shape[1] != level:
-            raise ValueError(f"assertion failed: ksk shape {tuple(ksk.shape)} != (in_dim, {level}, out_dim + 1)")
-        self.input_key_lwe_dimension = int(ksk.shape[0])
-        self.output_key_lwe_dimension = int(ksk.shape[2]) - 1
-        self.decomposition_base_log, self.decomposition_level_count = base_log, level
-        self.device = ksk.device
+        _key_fields(self, ksk, base_log, level)
         h = ctypes.c_void_p()
         check(lib().mi_lwe_ksk_create(_dev(ksk, "ksk"), self.input_key_lwe_dimension,
                                       self.output_key_lwe_dimension, base_log, level,
@@ -43,43 +63,15 @@ class LweKeyswitchKey:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_lwe_ksk_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_lwe_ksk_destroy")
 
 
 def keyswitch_lwe_ciphertext(lwe_keyswitch_key: LweKeyswitchKey, input_lwe_ciphertext, output_lwe_ciphertext) -> None:
     """output = keyswitch(input) for every ciphertext of the batch (lwe_keyswitch.rs:137-227)."""
-    k = lwe_keyswitch_key
-    n_in, n_out = k.input_key_lwe_dimension + 1, k.output_key_lwe_dimension + 1
-    if input_lwe_ciphertext.shape[-1] != n_in:
-        raise ValueError(f"assertion failed: Mismatched input LweDimension {input_lwe_ciphertext.shape[-1] - 1} "
-                         f"!= {k.input_key_lwe_dimension}")
-    if output_lwe_ciphertext.shape[-1] != n_out:
-        raise ValueError(f"assertion failed: Mismatched output LweDimension {output_lwe_ciphertext.shape[-1] - 1} "
-                         f"!= {k.output_key_lwe_dimension}")
-    batch = input_lwe_ciphertext.numel() // n_in
-    if output_lwe_ciphertext.numel() // n_out != batch:
-        raise ValueError("assertion failed: input and output batch sizes differ")
-    check(lib().mi_lwe_keyswitch_batch(k._h, _dev(output_lwe_ciphertext, "output_lwe_ciphertext"),
+    batch = _check_lwe_batch(lwe_keyswitch_key, input_lwe_ciphertext, output_lwe_ciphertext)
+    check(lib().mi_lwe_keyswitch_batch(lwe_keyswitch_key._h, _dev(output_lwe_ciphertext, "output_lwe_ciphertext"),
                                        _dev(input_lwe_ciphertext, "input_lwe_ciphertext"), batch,
                                        _stream(output_lwe_ciphertext)))
-
-
-def _dev32(t, name):
-    import torch
-
-    if not (type(t).__module__.startswith("torch") and t.is_cuda):
-        raise TypeError(f"{name} must be a HIP device tensor")
-    if t.dtype not in (torch.uint32, torch.int32):
-        raise TypeError(f"{name} must hold 32-bit integers, got {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class LweKeyswitchKey32:
@@ -90,13 +82,8 @@ class LweKeyswitchKey32:
     MSBs of the words as the reference stores non-native power-of-two moduli."""
 
     def __init__(self, ksk, base_log: int, level: int, out_modulus_log: int = 32):
-        if ksk.dim() != 3 or ksk.shape[1] != level:
-            raise ValueError(f"assertion failed: ksk shape {tuple(ksk.shape)} != (in_dim, {level}, out_dim + 1)")
-        self.input_key_lwe_dimension = int(ksk.shape[0])
-        self.output_key_lwe_dimension = int(ksk.shape[2]) - 1
-        self.decomposition_base_log, self.decomposition_level_count = base_log, level
+        _key_fields(self, ksk, base_log, level)
         self.out_modulus_log = out_modulus_log
-        self.device = ksk.device
         h = ctypes.c_void_p()
         check(lib().mi_lwe_ksk32_create(_dev32(ksk, "ksk"), self.input_key_lwe_dimension,
                                         self.output_key_lwe_dimension, base_log, level, out_modulus_log,
@@ -104,30 +91,15 @@ class LweKeyswitchKey32:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_lwe_ksk32_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_lwe_ksk32_destroy")
 
 
 def keyswitch_lwe_ciphertext_with_scalar_change(lwe_keyswitch_key: LweKeyswitchKey32, input_lwe_ciphertext,
                                                 output_lwe_ciphertext) -> None:
     """u32 output = keyswitch(u64 input) for every ciphertext of the batch (lwe_keyswitch.rs:331-447)."""
-    k = lwe_keyswitch_key
-    n_in, n_out = k.input_key_lwe_dimension + 1, k.output_key_lwe_dimension + 1
-    if input_lwe_ciphertext.shape[-1] != n_in:
-        raise ValueError(f"assertion failed: Mismatched input LweDimension {input_lwe_ciphertext.shape[-1] - 1} "
-                         f"!= {k.input_key_lwe_dimension}")
-    if output_lwe_ciphertext.shape[-1] != n_out:
-        raise ValueError(f"assertion failed: Mismatched output LweDimension {output_lwe_ciphertext.shape[-1] - 1} "
-                         f"!= {k.output_key_lwe_dimension}")
-    batch = input_lwe_ciphertext.numel() // n_in
-    if output_lwe_ciphertext.numel() // n_out != batch:
-        raise ValueError("assertion failed: input and output batch sizes differ")
-    check(lib().mi_lwe_keyswitch32_batch(k._h, _dev32(output_lwe_ciphertext, "output_lwe_ciphertext"),
+    batch = _check_lwe_batch(lwe_keyswitch_key, input_lwe_ciphertext, output_lwe_ciphertext)
+    check(lib().mi_lwe_keyswitch32_batch(lwe_keyswitch_key._h,
+                                         _dev32(output_lwe_ciphertext, "output_lwe_ciphertext"),
                                          _dev(input_lwe_ciphertext, "input_lwe_ciphertext"), batch,
                                          _stream(output_lwe_ciphertext)))
 

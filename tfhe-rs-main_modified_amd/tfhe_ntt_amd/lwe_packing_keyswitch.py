@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import check, lib
+from ._lib import check, lib, release
 from .ntt64_pbs import _dev, _stream
 
 
@@ -42,13 +42,7 @@ class LwePackingKeyswitchKey:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_lwe_pksk_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_lwe_pksk_destroy")
 
 
 def _check_glwe(k: LwePackingKeyswitchKey, glwe):

@@ -116,14 +116,9 @@ class DeviceSet:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                from ._lib import lib
-                lib().mi_multi_gpu_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        if getattr(self, "_h", None):
+            from ._lib import release
+            release(self, "mi_multi_gpu_destroy")
 
     def __len__(self):
         return len(self.devices)

@@ -15,7 +15,7 @@ from types import SimpleNamespace
 from typing import Optional
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, release
 
 _NONE_STATUSES = (_lib.MI_ERR_INVALID_ARG, _lib.MI_ERR_NOT_PRIME, _lib.MI_ERR_NO_ROOT)
 
@@ -39,13 +39,7 @@ class _NativePlan:
         return cls(h, n, device)
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_native_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_native_plan_destroy")
 
     def ntt_size(self) -> int:
         return self._n

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import MiError, check, lib
+from ._lib import MiError, check, lib, release
 
 SOLINAS = 0
 BNF = 1
@@ -29,16 +29,20 @@ MS_CENTERED = 1
 MS_PRE_SWITCHED = 2  # lwe_in already modulus-switched to [0, 2N) (ModulusSwitchedLweCiphertext)
 
 
-def _dev(t, name):
+def _dev(t, name, bits=64):
     import torch
 
     if not (type(t).__module__.startswith("torch") and t.is_cuda):
         raise TypeError(f"{name} must be a HIP device tensor")
-    if t.dtype not in (torch.uint64, torch.int64):
-        raise TypeError(f"{name} must hold 64-bit integers, got {t.dtype}")
+    if t.dtype not in ((torch.uint64, torch.int64) if bits == 64 else (torch.uint32, torch.int32)):
+        raise TypeError(f"{name} must hold {bits}-bit integers, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _dev32(t, name):
+    return _dev(t, name, 32)
 
 
 def _stream(t):
@@ -97,13 +101,7 @@ class NttGgswList:
         self._h = h
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_ntt64_ggsw_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_ntt64_ggsw_destroy")
 
 
 def _ext_prepared(pg, out, glwe, base_log, level, variant, cmux, ggsw_index):
@@ -197,13 +195,7 @@ class NttBootstrapKey:
         self.glwe_dimension, self.polynomial_size = k, plan.ntt_size()
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_pbs_ntt64_key_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_pbs_ntt64_key_destroy")
 
     def output_lwe_size(self) -> int:
         return self.glwe_dimension * self.polynomial_size + 1

@@ -11,7 +11,7 @@ import ctypes
 from typing import Optional
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, release
 from .prime64 import _is_torch
 
 _NONE_STATUSES = (_lib.MI_ERR_INVALID_ARG, _lib.MI_ERR_NOT_PRIME, _lib.MI_ERR_NO_ROOT)
@@ -37,13 +37,7 @@ class Plan:
         return cls(h, polynomial_size, modulus, device)
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().mi_ntt32_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        release(self, "mi_ntt32_plan_destroy")
 
     def ntt_size(self) -> int:
         return self._n

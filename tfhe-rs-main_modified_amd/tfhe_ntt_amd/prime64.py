@@ -21,7 +21,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import MiError, check, lib
+from ._lib import MiError, check, lib, release
 
 SOLINAS_P = 0xFFFFFFFF00000001
 
@@ -59,13 +59,8 @@ class Plan:
         return cls(h, polynomial_size, modulus, device, cached=True)
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and not getattr(self, "_cached", False):
-            try:
-                lib().mi_ntt64_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        if not getattr(self, "_cached", False):
+            release(self, "mi_ntt64_plan_destroy")
 
     @property
     def handle(self) -> ctypes.c_void_p:

@@ -46,6 +46,10 @@ def run_ks(engine, ksk, lwe, base_log, level):
     (50, 20, 6, 2, 33),         # r6 digit kernel at level 2 (one byte per digit), in_dim not a multiple of 32
     (70, 11, 5, 1, 300),        # ... at level 1, 2 row groups
     (24, 8, 3, 8, 9),           # ... at level 8 (native u64 output)
+    (20, 12, 32, 1, 17),        # digits wider than 32 bits: +2^31 at base 2^32 (5 bytes per digit)
+    (20, 12, 33, 1, 17),        # ... 2^33
+    (20, 12, 40, 1, 17),        # ... 2^40 (6 bytes per digit)
+    (20, 12, 63, 1, 17),        # ... 2^63 (8 bytes per digit)
 ])
 def test_keyswitch_matches_oracle(engine, oracle, in_dim, out_dim, base_log, level, batch):
     g = H.rng(in_dim * 7 + out_dim + base_log)

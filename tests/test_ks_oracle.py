@@ -12,26 +12,9 @@ import numpy as np
 import pytest
 
 import tfhe_helpers as H
+from decomp_corners import py_decompose  # noqa: F401  (test_ks32_oracle imports it from here)
 
 M64 = 2**64
-
-
-def py_decompose(x, base_log, level):
-    """decomposer.rs:156-185 + iter.rs:103-151 in plain Python integers (least significant first)."""
-    rep = base_log * level
-    res = x >> (64 - rep - 1)
-    rbit = res & 1
-    res = ((res + 1) >> 1) & ((1 << rep) - 1)
-    need = ((((res - 1) % M64) | (rbit << (rep - 1))) & res) >> (rep - 1)
-    state = (res - (need << rep)) % M64
-    terms = []
-    for _ in range(level):
-        r = state & ((1 << base_log) - 1)
-        state = (state >> base_log) | ((M64 - (1 << (64 - base_log))) if state >> 63 else 0)  # arithmetic shift
-        carry = ((((r - 1) % M64) | state) & r) >> (base_log - 1)
-        state = (state + carry) % M64
-        terms.append((r - (carry << base_log)) % M64)
-    return terms
 
 
 def py_keyswitch(ksk, lwe, base_log, level):

@@ -56,6 +56,7 @@ def run_pack(engine, pksk, lwe, base_log, level, lwe_per_glwe):
     (20, 2, 8, 4, 3, 5, 13),           # 24 columns padded to 32, lwe_per_glwe < N, three GLWEs
     (33, 1, 32, 10, 2, 32, 40),        # two bytes per digit
     (6, 1, 32, 21, 3, 32, 32),         # three bytes per digit
+    (10, 1, 16, 40, 1, 16, 20),        # a digit wider than 32 bits (six bytes)
     (50, 1, 64, 6, 2, 64, 320),        # level-2 digit kernel; GLWE boundaries inside 256-row groups
     (70, 1, 16, 5, 1, 16, 300),        # level 1
     (24, 3, 16, 3, 8, 16, 9),          # level 8; one partial GLWE

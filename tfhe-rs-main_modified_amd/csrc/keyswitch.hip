@@ -38,6 +38,7 @@
 #include "ntt64_launch.hpp"
 #include "keyswitch_launch.hpp"
 #include "ks_device.hpp"
+#include "ks_decomp.hpp"
 
 namespace mi {
 namespace ks {
@@ -45,41 +46,7 @@ namespace ks {
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 using u64 = uint64_t;
 
-// decomposer.rs:64-71 + :156-185 init_decomposer_state (native u64, closest representable).  pre_rounded: the
-// packing keyswitch decomposes closest_representable(input) (lwe_packing_keyswitch.rs:173-174), whose rounding bit
-// is 0, so the tie state 2^(rep-1) is balanced only when the bit below it is set; the state is otherwise the same.
-__device__ __forceinline__ u64 decomp_init(u64 input, int base_log, int level, bool pre_rounded = false) {
-  const unsigned rep = (unsigned)(base_log * level), non_rep = 64u - rep;
-  u64 res = input >> (non_rep - 1);
-  const u64 rounding_bit = pre_rounded ? 0u : res & 1u;
-  res += 1;
-  res >>= 1;
-  res &= (~0ull) >> (64u - rep);
-  const u64 need_balance = (((res - 1) | (rounding_bit << (rep - 1))) & res) >> (rep - 1);
-  return res - (need_balance << rep);
-}
-
-// iter.rs:131-151 decompose_one_level (arithmetic shift); the digit as a signed integer
-__device__ __forceinline__ int decompose_one(int base_log, u64& state) {
-  const u64 mask = (1ull << base_log) - 1;
-  const u64 res = state & mask;
-  state = (u64)((int64_t)state >> base_log);
-  const u64 carry = (((res - 1) | state) & res) >> (base_log - 1);
-  state += carry;
-  return (int)(int64_t)(res - (carry << base_log));
-}
-
-// signed byte t of x: x = sum_t s_t 2^(8t) mod 2^64, s_t in [-128, 127]
-__device__ __forceinline__ int8_t signed_byte(u64 x, int t) {
-  unsigned carry = 0;
-  int s = 0;
-  for (int u = 0; u <= t; ++u) {
-    const unsigned v = (unsigned)((x >> (8 * u)) & 255u) + carry;
-    carry = v >= 128u;
-    s = (int)v - (carry ? 256 : 0);
-  }
-  return (int8_t)s;
-}
+// decomp_init, decompose_one, signed_byte: ks_decomp.hpp (host-callable, checked by tests/cpp/ks_decomp_check.cpp)
 
 struct Shape {
   uint32_t in_dim, out_size, level, base_log, nd, K, KB, CT;
@@ -176,7 +143,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     uint32_t sb = k0 - kd0 * s.nd, i = kd0 / s.level, li = kd0 - i * s.level;
     const bool live = row < batch;
     u64 state = 0;
-    int d = 0;
+    int64_t d = 0;
     if (live && k0 < s.K) {  // the state after terms 0..li of coefficient i
       state = decomp_init(x[i], bl, lv, pre);
       for (uint32_t u = 0; u <= li; ++u) d = decompose_one(bl, state);
@@ -184,7 +151,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     for (int j = 0; j < 16; ++j) {
       const uint32_t k = k0 + j;
       const bool on = live && k + 1 < s.K;
-      b[j] = (live && k < s.K) ? signed_byte((u64)(int64_t)d, (int)sb) : 0;
+      b[j] = (live && k < s.K) ? signed_byte((u64)d, (int)sb) : 0;
       if (++sb == s.nd) {  // next decomposition term
         sb = 0;
         if (++li == s.level) {  // next mask coefficient

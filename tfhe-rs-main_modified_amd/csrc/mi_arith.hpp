@@ -25,11 +25,19 @@ typedef uint32_t u32;
 static constexpr u64 GL_P = 0xFFFFFFFF00000001ull;
 static constexpr u64 GL_EPS = 0xFFFFFFFFull;  // 2^64 mod p = 2^32 - 1
 
-__device__ __forceinline__ u32 lo32(u64 x) { return (u32)x; }
-__device__ __forceinline__ u32 hi32(u64 x) { return (u32)(x >> 32); }
+__host__ __device__ __forceinline__ u32 lo32(u64 x) { return (u32)x; }
+__host__ __device__ __forceinline__ u32 hi32(u64 x) { return (u32)(x >> 32); }
+// high half of a 32 x 32 product: v_mul_hi_u32 on the device; the host form serves tests/cpp/arith_check.cpp
+__host__ __device__ __forceinline__ u32 umulhi32(u32 a, u32 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umulhi(a, b);
+#else
+  return (u32)(((u64)a * b) >> 32);
+#endif
+}
 
 // 64x64 -> 128 with four 32x32+64 multiply-adds (v_mad_u64_u32).
-__device__ __forceinline__ void mul64x64(u64 a, u64 b, u64 &lo, u64 &hi) {
+__host__ __device__ __forceinline__ void mul64x64(u64 a, u64 b, u64 &lo, u64 &hi) {
   const u32 a0 = lo32(a), a1 = hi32(a), b0 = lo32(b), b1 = hi32(b);
   const u64 p00 = (u64)a0 * b0;
   const u64 p10 = (u64)a1 * b0 + (p00 >> 32);
@@ -44,32 +52,32 @@ struct Goldilocks {
 
   // a + b mod p.  If the 64-bit add carries, s + (2^32-1) is already canonical; otherwise
   // subtract p (= add 2^32-1 mod 2^64) when s >= p.
-  __device__ __forceinline__ static u64 add(u64 a, u64 b) {
+  __host__ __device__ __forceinline__ static u64 add(u64 a, u64 b) {
     const u64 s = a + b;
     const bool c = s < a;
     return (c || s >= P) ? s + GL_EPS : s;
   }
   // a - b mod p.  On borrow, d + p = d - (2^32-1) (mod 2^64) and cannot underflow.
-  __device__ __forceinline__ static u64 sub(u64 a, u64 b) {
+  __host__ __device__ __forceinline__ static u64 sub(u64 a, u64 b) {
     const u64 d = a - b;
     return (a < b) ? d - GL_EPS : d;
   }
   // Lazy forms (r5) for butterfly chains whose values need only be congruent mod p (any 64-bit value) until a final
   // multiply or canonicalisation: a + t for a canonical t and any a (a carry folds as + EPS and cannot carry again:
   // a + t - 2^64 < a - EPS + 1), a - t for a canonical t (a borrow subtracts EPS: a - t + 2^64 > EPS, no wrap)
-  __device__ __forceinline__ static u64 add_lazy(u64 a, u64 t) {
+  __host__ __device__ __forceinline__ static u64 add_lazy(u64 a, u64 t) {
     unsigned long long c;
     const u64 s = __builtin_addcll(a, t, 0ull, &c);  // the add's own carry (not a 64-bit compare)
     return s + (c ? GL_EPS : 0);
   }
-  __device__ __forceinline__ static u64 sub_lazy(u64 a, u64 t) {
+  __host__ __device__ __forceinline__ static u64 sub_lazy(u64 a, u64 t) {
     unsigned long long b;
     const u64 d = __builtin_subcll(a, t, 0ull, &b);
     return d - (b ? GL_EPS : 0);
   }
-  __device__ __forceinline__ static u64 canon(u64 x) { return x >= P ? x - P : x; }
+  __host__ __device__ __forceinline__ static u64 canon(u64 x) { return x >= P ? x - P : x; }
   // (hi:lo) mod p for any 128-bit value: hi = hh*2^32 + hl, 2^96 = -1, 2^64 = 2^32 - 1.
-  __device__ __forceinline__ static u64 reduce128(u64 lo, u64 hi) {
+  __host__ __device__ __forceinline__ static u64 reduce128(u64 lo, u64 hi) {
     const u32 hh = hi32(hi), hl = lo32(hi);
     u64 t0 = lo - (u64)hh;
     t0 = (lo < (u64)hh) ? t0 - GL_EPS : t0;
@@ -78,7 +86,7 @@ struct Goldilocks {
     const bool c = r < t1;
     return (c || r >= P) ? r + GL_EPS : r;
   }
-  __device__ __forceinline__ static u64 mul(u64 a, u64 b) {
+  __host__ __device__ __forceinline__ static u64 mul(u64 a, u64 b) {
     u64 lo, hi;
     mul64x64(a, b, lo, hi);
     return reduce128(lo, hi);
@@ -86,7 +94,7 @@ struct Goldilocks {
   // |x 2^e| mod p for a twiddle 2^e (e < 192; 2^96 = -1), canonical, with the sign in `neg` (x 2^e = neg ? -t : t):
   // shifts and the 128-bit reduction instead of the four-limb product.  e must fold to a constant (unrolled stage
   // loops) so the branches disappear.  The friendly twiddles of prime64.rs:162-177.
-  __device__ __forceinline__ static u64 mul_pow2(u64 x, int e, bool& neg) {
+  __host__ __device__ __forceinline__ static u64 mul_pow2(u64 x, int e, bool& neg) {
     neg = e >= 96;
     const int f = neg ? e - 96 : e;
     if (f == 0) return x >= P ? x - P : x;
@@ -110,15 +118,15 @@ __host__ __device__ constexpr int tower_exp(bool fwd, int s, int g) {
 // Generic odd modulus p < 2^64 in Montgomery form (R = 2^64).  `pinv` = -p^{-1} mod 2^64.
 struct Montgomery {
   u64 p, pinv, r2;  // r2 = R^2 mod p (to enter Montgomery form on device)
-  __device__ __forceinline__ u64 add(u64 a, u64 b) const {
+  __host__ __device__ __forceinline__ u64 add(u64 a, u64 b) const {
     const u64 neg_b = p - b;
     return a >= neg_b ? a - neg_b : a + b;
   }
-  __device__ __forceinline__ u64 sub(u64 a, u64 b) const {
+  __host__ __device__ __forceinline__ u64 sub(u64 a, u64 b) const {
     return a >= b ? a - b : a + (p - b);
   }
   // REDC(a*b): a < p, b < p  ->  a*b*R^-1 mod p, canonical.
-  __device__ __forceinline__ u64 mul(u64 a, u64 b) const {
+  __host__ __device__ __forceinline__ u64 mul(u64 a, u64 b) const {
     u64 tlo, thi;
     mul64x64(a, b, tlo, thi);
     const u64 m = tlo * pinv;
@@ -141,18 +149,18 @@ struct Montgomery {
 // residues as the Montgomery form's (bit-exact).
 struct Shoup32 {
   uint32_t p;
-  __device__ __forceinline__ u64 add(u64 a, u64 b) const {
+  __host__ __device__ __forceinline__ u64 add(u64 a, u64 b) const {
     const uint32_t x = (uint32_t)a, y = (uint32_t)b, neg_y = p - y;
     return x >= neg_y ? x - neg_y : x + y;
   }
-  __device__ __forceinline__ u64 sub(u64 a, u64 b) const {
+  __host__ __device__ __forceinline__ u64 sub(u64 a, u64 b) const {
     const uint32_t x = (uint32_t)a, y = (uint32_t)b;
     return x >= y ? x - y : x + (p - y);
   }
   // x < 2^32, wv = w | w' << 32 with w < p
-  __device__ __forceinline__ u64 mul(u64 a, u64 wv) const {
+  __host__ __device__ __forceinline__ u64 mul(u64 a, u64 wv) const {
     const uint32_t x = (uint32_t)a, w = (uint32_t)wv, wq = (uint32_t)(wv >> 32);
-    const uint32_t q = __umulhi(x, wq);
+    const uint32_t q = umulhi32(x, wq);
     const u64 r = (u64)x * w - (u64)q * p;
     return r >= p ? r - p : r;
   }

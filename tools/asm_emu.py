@@ -27,7 +27,40 @@ def _word(m):
     return int((b[:32] << SH).sum()) | (int((b[32:] << SH).sum()) << 32)
 
 
+class CarryRecorder:
+    """Opt-in record of which carry / borrow outcomes a run produced (Wave.rec, run_body(record=...); off by default and
+    without effect on any result).  A site is an instruction, named by its index in the body's line list, that writes
+    a lane mask (an SGPR pair or VCC) some later instruction reads; per site: whether a 0 and whether a 1 occurred in
+    an active lane.  Masks nobody reads (the junk carry destination) never become sites.  One recorder may collect
+    over many runs of the same body."""
+
+    def __init__(self):
+        self.seen = {}      # line index -> [saw a 0, saw a 1]
+        self.read = set()   # line indices whose mask was read before being overwritten
+        self._writer = {}   # SGPR pair base -> line index of the mask's last writer (per run)
+
+    def start_run(self):
+        self._writer = {}
+
+    def wrote(self, base, line, m, active):
+        s = self.seen.setdefault(line, [False, False])
+        s[0] |= bool((~m & active).any())
+        s[1] |= bool((m & active).any())
+        self._writer[base] = line
+
+    def was_read(self, base):
+        w = self._writer.get(base)
+        if w is not None:
+            self.read.add(w)
+
+    def sites(self):
+        """{line index: (saw 0, saw 1)} of the masks that were read."""
+        return {l: tuple(s) for l, s in self.seen.items() if l in self.read}
+
+
 class Wave:
+    rec = None  # a CarryRecorder, or None
+
     def __init__(self, ops, mem, lds=None, lds_bytes=65536):
         self.v = np.zeros((256, LANES), dtype=np.uint64)   # 32-bit values kept in uint64
         self.s = np.zeros(128, dtype=np.uint64)
@@ -59,12 +92,16 @@ class Wave:
         b = self.VCC if tok == "vcc" else self.spair(tok)
         if b is None:
             raise ValueError(tok)
+        if self.rec is not None:
+            self.rec.was_read(b)
         return _bits(int(self.s[b]) | (int(self.s[b + 1]) << 32))
 
     def set_mask(self, tok, m):
         m = m & self.exec  # a VALU lane-mask write clears the bits of inactive lanes
         word = _word(m)
-        b = self.spair(tok)
+        b = self.VCC if tok == "vcc" else self.spair(tok)
+        if self.rec is not None:
+            self.rec.wrote(b, self.line, m, self.exec)
         self.s[b] = np.uint64(word & 0xFFFFFFFF)
         self.s[b + 1] = np.uint64(word >> 32)
 
@@ -95,8 +132,10 @@ class Wave:
 
     # ---- execution ------------------------------------------------------------------------------
     def load(self, lines):
-        self.prog, self.labels = [], {}
-        for line in lines:
+        self.prog, self.labels, self.line = [], {}, -1
+        if self.rec is not None:
+            self.rec.start_run()
+        for src, line in enumerate(lines):
             line = line.strip()
             for k, v in self.ops.items():
                 line = line.replace(f"%[{k}]", v)
@@ -111,13 +150,13 @@ class Wave:
             fn = getattr(self, "op_" + mn, None)
             if fn is None:
                 raise NotImplementedError(mn)
-            self.prog.append((fn, args, mn))
+            self.prog.append((fn, args, mn, src))
         self.pc = 0
 
     def steps(self):
         """Generator: runs to the end, yielding at every s_barrier."""
         while self.pc < len(self.prog):
-            fn, args, mn = self.prog[self.pc]
+            fn, args, mn, self.line = self.prog[self.pc]
             self.pc += 1
             if mn == "s_barrier":
                 yield
@@ -298,11 +337,16 @@ class Wave:
         self.scc = int(m.any())
         return True
 
+    def _rec_salu(self, base, word):
+        if self.rec is not None:  # a lane mask combined on the SALU is a site like the VALU carries it reads
+            self.rec.wrote(base, self.line, _bits(word), self.exec)
+
     def op_s_not_b64(self, a):
         if self._set_exec_or(a, ~self.mask(a[1])):
             return
         word = _word(~self.mask(a[1]))
         b = self.VCC if a[0] == "vcc" else self.spair(a[0])
+        self._rec_salu(b, word)
         self.s[b], self.s[b + 1] = np.uint64(word & 0xFFFFFFFF), np.uint64(word >> 32)
         self.scc = int(word != 0)
 
@@ -311,12 +355,14 @@ class Wave:
             return
         word = _word(self.mask(a[1]) | self.mask(a[2]))
         b = self.spair(a[0])
+        self._rec_salu(b, word)
         self.s[b], self.s[b + 1] = np.uint64(word & 0xFFFFFFFF), np.uint64(word >> 32)
         self.scc = int(word != 0)
 
     def op_s_andn2_b64(self, a):
         word = _word(self.mask(a[1]) & ~self.mask(a[2]))
         b = self.spair(a[0])
+        self._rec_salu(b, word)
         self.s[b], self.s[b + 1] = np.uint64(word & 0xFFFFFFFF), np.uint64(word >> 32)
         self.scc = int(word != 0)
 
@@ -425,12 +471,13 @@ def body_lines(hdr, name, prefix="MI_TW_BODY_"):
 
 
 def run_body(hdr, name, poly, twist_tab, fwd=True, out_of_place=False, mem_extra=None, ops_extra=None, out_init=None,
-             w1x=None):
+             w1x=None, record=None):
     """Emulate one wave (wave 0 of a workgroup) of the transform body on one polynomial.  out_of_place: the body
     writes another buffer (%[o_lo] / %[o_hi], the key-conversion body), which is returned.  mem_extra / ops_extra:
     more memory regions (base address -> u64 array) and operand bindings (the MAC-fused inverse's term bases).
     out_init: the %[o_*] buffer's initial contents (the Ntt64View add_backward bodies read and write it); the call then
-    returns (data, out).  w1x (default: the generator's FWD_W1X for forward bodies, i.e. names starting "fwd"): the
+    returns (data, out).  record: a CarryRecorder that collects this run's carry outcomes (line indices are those of
+    body_lines(hdr, name)).  w1x (default: the generator's FWD_W1X for forward bodies, i.e. names starting "fwd"): the
     forward's W1x lane-pair layout (lane = i + 32 j0) and its transpose addresses, as ntt64_tw_device.hpp computes them."""
     data = np.array(poly, dtype=np.uint64).copy()
     tw = np.array(twist_tab, dtype=np.uint64)
@@ -443,6 +490,7 @@ def run_body(hdr, name, poly, twist_tab, fwd=True, out_of_place=False, mem_extra
     ops = {"g_lo": f"{GB & 0xFFFFFFFF}", "g_hi": f"{GB >> 32}", "tw_lo": f"{TB & 0xFFFFFFFF}", "tw_hi": f"{TB >> 32}",
            "o_lo": f"{OB & 0xFFFFFFFF}", "o_hi": f"{OB >> 32}"}
     w = Wave(None, mem)
+    w.rec = record
     vin = {"l8": lane * 8, "t1w": S + (lane & 31) * 8, "t1r": S + (i * 34 + par) * 8, "lwo": par * 128,
            "t2wl": S + ((i & 15) * 66 + 33 * par) * 8, "t2wh": S + ((i & 15) * 66 + 31 * par + 1) * 8,
            "t2r": S + (lane ^ (lane >> np.uint64(5))) * 8, "t4w": S + ((i & 15) * 66 + par) * 8, "t4r": S + lane * 8,

@@ -65,6 +65,25 @@ def expand(r):
     return [r]
 
 
+class Line(str):
+    """An instruction's text that remembers which generator function emitted it and where in that function
+    (`origin` = (function name, source line relative to the function's `def`, shift exponent if any)): the key under which
+    tests/test_tw_body_corners.py names a carry site, since the list scheduler moves program counters freely.  Prints
+    and compares as the plain text."""
+
+    def __new__(cls, text, origin):
+        self = super().__new__(cls, text)
+        self.origin = origin
+        return self
+
+
+def _origin():
+    f = sys._getframe(2)  # the caller of Seg.add / Seg.add_masked
+    loc = f.f_locals      # the shift exponent(s) mod 96 of the power-of-two multiplies, None elsewhere
+    e = loc.get("e") if "e" in loc else ((loc["e0"], loc["e1"]) if "e0" in loc and "e1" in loc else None)
+    return f.f_code.co_name, f.f_lineno - f.f_code.co_firstlineno, e
+
+
 class Seg:
     """A list of ops in sequential program order, list-scheduled with gfx950 hazard padding:
     VALU write of an SGPR -> VALU read: 2 wait states; -> SALU read: 1; VALU write of a VGPR ->
@@ -74,14 +93,14 @@ class Seg:
         self.ops = []
 
     def add(self, text, reads=(), writes=(), kind="valu"):
-        self.ops.append(Op(text, reads, writes, kind))
+        self.ops.append(Op(Line(text, _origin()) if isinstance(text, str) else text, reads, writes, kind))
 
     def add_masked(self, set_line, set_reads, text, reads=(), writes=()):
         """One VALU instruction under EXEC = a lane mask the SALU `set_line` writes from the SGPR pairs `set_reads`
         (carry / borrow masks of earlier VALU ops), EXEC restored to the saved full mask right after.  Scheduled as one
         unit; the SALU read of the mask obeys the VALU-write -> SALU-read wait state.  Back-to-back masked units drop
         the restore between them (masked_peephole)."""
-        op = Op([set_line, text, EXEC_RESTORE], list(reads) + list(set_reads), writes)
+        op = Op([set_line, Line(text, _origin()), EXEC_RESTORE], list(reads) + list(set_reads), writes)
         for r in set_reads:
             op.mask_reads.update(expand(r))
         self.ops.append(op)

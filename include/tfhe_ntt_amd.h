@@ -430,6 +430,37 @@ int mi_fft64_pbs_batch_lut_indexed(const mi_fft64_pbs_key *key, uint64_t *lwe_ou
  * ModulusSwitchedLweCiphertext input: MI_MS_PRE_SWITCHED, or the native LWE switched on the device). */
 int mi_fft64_blind_rotate_batch(const mi_fft64_pbs_key *key, uint64_t *acc_glwe, const uint64_t *lwe_in, size_t batch,
                                 int ms_mode, void *stream);
+/* The multi-bit programmable bootstrap on the f64-FFT path (algorithms/lwe_multi_bit_programmable_bootstrapping.rs:
+ * multi_bit_deterministic_blind_rotate_assign :644-869, prepare_multi_bit_ggsw_mem_optimized :115-154,
+ * modulus_switch_multi_bit :30-51, selection_bit :55-65; key layout lwe_multi_bit_bootstrap_key_generation.rs:398-421).
+ * The key is referenced (the caller keeps `fbsk` alive): (n_lwe / g) x 2^g x level x (k+1) x (k+1) x N/2 complex,
+ * group-major, each GGSW in this engine's order with the highest level first as for mi_fft64_pbs_key_create
+ * (mi_bsk_to_fourier64 converts the standard key, whatever its polynomial count); GGSW idx of group i encrypts
+ * prod_m (s[i g + m] XOR NOT bit_m(idx)), bit_m(idx) = (idx >> (g - 1 - m)) & 1.  One blind-rotation step handles g mask
+ * elements: n_lwe / g external products.  _create: MI_ERR_INVALID_ARG for a NULL argument, a grouping factor outside
+ * {2, 3, 4}, n_lwe not a multiple of it, base_log * level outside [1, 63]; MI_ERR_UNSUPPORTED for N != 2048 or k
+ * outside {1, 2}.  The input is always the native LWE, switched on the device with the standard switch of the wrapping
+ * sum of each subset of a group's mask elements (there is no ms_mode); the rotation order is fixed, so this is the
+ * reference's deterministic variant. */
+typedef struct mi_fft64_multi_bit_pbs_key mi_fft64_multi_bit_pbs_key;
+int mi_fft64_multi_bit_pbs_key_create(const mi_fft64_plan *plan, const double *fbsk, size_t n_lwe, int k, int base_log,
+                                      int level, int grouping_factor, mi_fft64_multi_bit_pbs_key **out_key);
+int mi_fft64_multi_bit_pbs_key_destroy(mi_fft64_multi_bit_pbs_key *key);
+int mi_fft64_multi_bit_pbs_key_info(const mi_fft64_multi_bit_pbs_key *key, size_t *n_lwe, int *k, int *base_log,
+                                    int *level, int *grouping_factor);
+/* multi_bit_programmable_bootstrap_lwe_ciphertext (lwe_multi_bit_programmable_bootstrapping.rs:1029-1126): one shared
+ * accumulator `lut` ((k+1) N u64), sample 0 of the rotated accumulator into lwe_out[b] (k N + 1 u64). */
+int mi_fft64_multi_bit_pbs_batch(const mi_fft64_multi_bit_pbs_key *key, uint64_t *lwe_out, const uint64_t *lwe_in,
+                                 const uint64_t *lut, size_t batch, void *stream);
+/* As mi_fft64_pbs_batch_lut_indexed: lut_index NULL = one accumulator per item (n_lut >= batch); otherwise item b uses
+ * GLWE lut_index[b] (device u32) and an index >= n_lut leaves lwe_out[b] untouched. */
+int mi_fft64_multi_bit_pbs_batch_lut_indexed(const mi_fft64_multi_bit_pbs_key *key, uint64_t *lwe_out,
+                                             const uint64_t *lwe_in, const uint64_t *lut_list,
+                                             const uint32_t *lut_index, size_t n_lut, size_t batch, void *stream);
+/* multi_bit_blind_rotate_assign (:644-869), batched and in place, GLWE in and GLWE out as mi_fft64_blind_rotate_batch:
+ * acc_glwe[b] is divided by X^ms(body) and taken through the n_lwe / g steps acc <- bundle (.) acc. */
+int mi_fft64_multi_bit_blind_rotate_batch(const mi_fft64_multi_bit_pbs_key *key, uint64_t *acc_glwe,
+                                          const uint64_t *lwe_in, size_t batch, void *stream);
 /* The multi-GPU bootstrap of mi_pbs_ntt64_multi_gpu[_ordered] (same sharding, active-GPU count, scatter / gather and
  * producer-stream ordering) on the f64-FFT path: keys[i] (bound to a plan of devices[i], same shape) and luts[i] on
  * devices[i], lwe_in / lwe_out on devices[0]. */

@@ -24,7 +24,8 @@ namespace {
 
 constexpr size_t FFT_N = 2048, FFT_M = 1024;
 constexpr size_t GEN_MIN_N = 32, GEN_MAX_N = (size_t)1 << 18;
-constexpr size_t OFF_T2 = 2 * 1024, OFF_CM = OFF_T2 + 2 * 64, OFF_CMI = OFF_CM + 2 * 16, TABLE_DOUBLES = OFF_CMI + 2 * 16;
+constexpr size_t OFF_T2 = 2 * 1024, OFF_CM = OFF_T2 + 2 * 64, OFF_CMI = OFF_CM + 2 * 16, OFF_ROOTS = OFF_CMI + 2 * 16;
+constexpr size_t TABLE_DOUBLES = OFF_ROOTS + 2 * 2 * FFT_N;
 
 // exp(i pi e / 2048) for an integer exponent (reduced exactly mod 4096 first), in long double
 void unit_root(long e, double* re, double* im) {
@@ -53,6 +54,8 @@ std::vector<double> host_tables() {
     h[OFF_CMI + 2 * m] = re / (double)FFT_M;  // exact scaling (a power of two): 1 / M
     h[OFF_CMI + 2 * m + 1] = im / (double)FFT_M;
   }
+  // roots[j] = zeta^j = exp(i pi j / N), j < 2N
+  for (size_t j = 0; j < 2 * FFT_N; ++j) unit_root((long)j, &h[OFF_ROOTS + 2 * j], &h[OFF_ROOTS + 2 * j + 1]);
   return h;
 }
 
@@ -108,7 +111,8 @@ int make_plan(size_t n, int device, mi_fft64_plan** out) {
     const size_t m = n / 2;
     p->gtables = {p->d_tables, p->d_tables + 2 * m, p->d_tables + 4 * m, __builtin_ctzll((unsigned long long)n)};
   } else {
-    p->tables = {p->d_tables, p->d_tables + OFF_T2, p->d_tables + OFF_CM, p->d_tables + OFF_CMI};
+    p->tables = {p->d_tables, p->d_tables + OFF_T2, p->d_tables + OFF_CM, p->d_tables + OFF_CMI,
+                 p->d_tables + OFF_ROOTS};
   }
   *out = p;
   return MI_OK;
@@ -534,6 +538,105 @@ int mi_fft64_blind_rotate_batch(const mi_fft64_pbs_key* key, uint64_t* acc_glwe,
   io.per_item = 1;
   io.glwe_out = acc_glwe;
   return fft_pbs_common(key, nullptr, lwe_in, io, batch, ms_mode, stream);
+}
+
+}  // extern "C"
+
+// ---- the multi-bit PBS (algorithms/lwe_multi_bit_programmable_bootstrapping.rs:644-869; fft64_multi_bit.hip) --------
+extern "C" {
+
+int mi_fft64_multi_bit_pbs_key_create(const mi_fft64_plan* plan, const double* fbsk, size_t n_lwe, int k, int base_log,
+                                      int level, int grouping_factor, mi_fft64_multi_bit_pbs_key** out_key) {
+  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
+  *out_key = nullptr;
+  if (!plan) return fail(MI_ERR_INVALID_ARG, "plan is NULL");
+  if (!fbsk) return fail(MI_ERR_INVALID_ARG, "bsk is NULL");
+  if (grouping_factor < 2 || grouping_factor > 4) return fail(MI_ERR_INVALID_ARG, "grouping factor must be 2, 3 or 4");
+  if (n_lwe == 0 || n_lwe > 0xFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "n_lwe out of range");
+  if (n_lwe % (size_t)grouping_factor)
+    return fail(MI_ERR_INVALID_ARG, "n_lwe must be a multiple of the grouping factor");
+  if (level < 1 || base_log < 1 || base_log > 63 || base_log * level > 63)
+    return fail(MI_ERR_INVALID_ARG, "decomposition base_log * level must be in [1, 63]");
+  if (plan->generic) return fail(MI_ERR_UNSUPPORTED, "the multi-bit PBS runs at N = 2048");
+  if (k < 1 || k > 2) return fail(MI_ERR_UNSUPPORTED, "the multi-bit PBS runs for k in {1, 2}");
+  auto* key = new (std::nothrow) mi_fft64_multi_bit_pbs_key;
+  if (!key) return fail(MI_ERR_OOM, "host allocation failed");
+  key->plan = plan;
+  key->fbsk = fbsk;
+  key->n_lwe = n_lwe;
+  key->k = k;
+  key->base_log = base_log;
+  key->level = level;
+  key->grouping_factor = grouping_factor;
+  *out_key = key;
+  return MI_OK;
+}
+
+int mi_fft64_multi_bit_pbs_key_destroy(mi_fft64_multi_bit_pbs_key* key) {
+  delete key;
+  return MI_OK;
+}
+
+int mi_fft64_multi_bit_pbs_key_info(const mi_fft64_multi_bit_pbs_key* key, size_t* n_lwe, int* k, int* base_log,
+                                    int* level, int* grouping_factor) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (n_lwe) *n_lwe = key->n_lwe;
+  if (k) *k = key->k;
+  if (base_log) *base_log = key->base_log;
+  if (level) *level = key->level;
+  if (grouping_factor) *grouping_factor = key->grouping_factor;
+  return MI_OK;
+}
+
+}  // extern "C"
+
+static int multi_bit_common(const mi_fft64_multi_bit_pbs_key* key, uint64_t* lwe_out, const uint64_t* lwe_in,
+                            const mi::PbsIo& io, size_t batch, void* stream) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (batch == 0) return MI_OK;
+  if ((!lwe_out && !io.glwe_out) || !lwe_in || !io.lut) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (batch > 0x7FFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
+  DeviceGuard g(key->plan->device);
+  const hipError_t e =
+      mi::launch_fft64_multi_bit_pbs(key->k, key->grouping_factor, lwe_out, lwe_in, io, key->fbsk, key->n_lwe, batch,
+                                     key->base_log, key->level, key->plan->tables, (hipStream_t)stream);
+  return e == hipSuccess ? MI_OK : hip_fail(e, "fft64 multi-bit pbs launch");
+}
+
+extern "C" {
+
+int mi_fft64_multi_bit_pbs_batch(const mi_fft64_multi_bit_pbs_key* key, uint64_t* lwe_out, const uint64_t* lwe_in,
+                                 const uint64_t* lut, size_t batch, void* stream) {
+  if (key && batch && !lwe_out) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  mi::PbsIo io;
+  io.lut = lut;
+  return multi_bit_common(key, lwe_out, lwe_in, io, batch, stream);
+}
+
+int mi_fft64_multi_bit_pbs_batch_lut_indexed(const mi_fft64_multi_bit_pbs_key* key, uint64_t* lwe_out,
+                                             const uint64_t* lwe_in, const uint64_t* lut_list,
+                                             const uint32_t* lut_index, size_t n_lut, size_t batch, void* stream) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (batch && !lwe_out) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (n_lut == 0 || n_lut > 0xFFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "n_lut out of range");
+  if (!lut_index && n_lut < batch) return fail(MI_ERR_INVALID_ARG, "per-item LUTs: n_lut < batch");
+  mi::PbsIo io;
+  io.lut = lut_list;
+  io.lut_idx = lut_index;
+  io.n_lut = (uint32_t)n_lut;
+  io.per_item = lut_index ? 0 : 1;
+  return multi_bit_common(key, lwe_out, lwe_in, io, batch, stream);
+}
+
+int mi_fft64_multi_bit_blind_rotate_batch(const mi_fft64_multi_bit_pbs_key* key, uint64_t* acc_glwe,
+                                          const uint64_t* lwe_in, size_t batch, void* stream) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (batch && !acc_glwe) return fail(MI_ERR_INVALID_ARG, "acc_glwe is NULL");
+  mi::PbsIo io;
+  io.lut = acc_glwe;
+  io.per_item = 1;
+  io.glwe_out = acc_glwe;
+  return multi_bit_common(key, nullptr, lwe_in, io, batch, stream);
 }
 
 }  // extern "C"

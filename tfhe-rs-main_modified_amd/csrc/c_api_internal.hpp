@@ -57,8 +57,8 @@ struct mi_fft64_plan {
   int device = 0;
   bool cached = false;
   bool generic = false;        // the shape-generic engine (N != 2048)
-  double* d_tables = nullptr;  // N = 2048: t1 (2048) | t2 (96, padded to 128) | cm (32) | cmi (32) doubles;
-                               // generic: tw | untw | wm (M complex each)
+  double* d_tables = nullptr;  // N = 2048: t1 (2048) | t2 (96, padded to 128) | cm (32) | cmi (32) | roots (8192)
+                               // doubles; generic: tw | untw | wm (M complex each)
   mi::FftTables tables{};
   mi::FftGenTables gtables{};
 };
@@ -69,6 +69,13 @@ struct mi_fft64_pbs_key {
   double* owned = nullptr;       // device copy made by mi_fft64_pbs_key_load
   size_t n_lwe = 0;
   int k = 1, base_log = 0, level = 0;
+};
+
+struct mi_fft64_multi_bit_pbs_key {
+  const mi_fft64_plan* plan = nullptr;
+  const double* fbsk = nullptr;  // caller-owned: (n_lwe / g) x 2^g Fourier GGSWs
+  size_t n_lwe = 0;
+  int k = 1, base_log = 0, level = 0, grouping_factor = 0;
 };
 
 // a GGSW list made ready for the external product / CMUX (mi_ntt64_ggsw_create): the fused N = 2048 level-1 bodies read

@@ -14,11 +14,13 @@ namespace mi {
 //   t2  [3][16]   W64^(jl q1) = exp(-2 pi i jl q1 / 64), q1 = 1..3
 //   cm  [16]      exp(i pi m / 32)
 //   cmi [16]      exp(-i pi m / 32) / M  (torus units; the API backward applies the 2^64)
+//   roots [2N]    zeta^j = exp(i pi j / N): the monomial phases of the multi-bit PBS (fft64_multi_bit.hip)
 struct FftTables {
   const double* t1;
   const double* t2;
   const double* cm;
   const double* cmi;
+  const double* roots;
 };
 
 hipError_t launch_fft64_fwd_torus(double* fourier, const uint64_t* std_, size_t batch, const FftTables& t,
@@ -30,6 +32,11 @@ hipError_t launch_fft64_ext_product(int k, bool cmux, uint64_t* out, uint64_t* g
 hipError_t launch_fft64_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const PbsIo& io, const double* fbsk,
                             size_t n_lwe, size_t batch, int base_log, int level, int ms_mode, const FftTables& t,
                             hipStream_t s);
+// the multi-bit PBS (fft64_multi_bit.hip): fbsk = (n_lwe / g) x 2^g GGSWs, g = grouping_factor in {2, 3, 4} dividing n_lwe;
+// the input is the native LWE, switched with the standard switch
+hipError_t launch_fft64_multi_bit_pbs(int k, int grouping_factor, uint64_t* out, const uint64_t* lwe_in,
+                                      const PbsIo& io, const double* fbsk, size_t n_lwe, size_t batch, int base_log,
+                                      int level, const FftTables& t, hipStream_t s);
 // Fourier order interchange of `polys` polynomials (N / 2 complex each; in place allowed): to_standard = engine
 // order -> the reference's serialised natural order (tfhe-fft/src/unordered.rs:943-964), else the reverse (:974-1020)
 hipError_t launch_fft64_reorder(double* out, const double* in, size_t polys, bool to_standard, hipStream_t s);

@@ -9,6 +9,9 @@ Names follow the reference (paths relative to /root/reference/tfhe/src/core_cryp
 * ``FourierLweBootstrapKey``, ``programmable_bootstrap_lwe_ciphertext``  fft64_pbs.rs:924-1060
 * ``batch_programmable_bootstrap_lwe_ciphertext`` (one accumulator per input), ``blind_rotate_assign``
                                                      fft64_pbs.rs:1055-1127, 186-250
+* ``FourierLweMultiBitBootstrapKey``, ``multi_bit_programmable_bootstrap_lwe_ciphertext``,
+  ``multi_bit_blind_rotate_assign``                  algorithms/lwe_multi_bit_programmable_bootstrapping.rs:644-869,
+                                                     1029-1126 (N = 2048, k in {1, 2}, grouping factor 2, 3 or 4)
 * ``Fft.to_standard_order`` / ``from_standard_order``  the serialised (natural) Fourier order of
   tfhe-fft/src/unordered.rs:943-1020; ``FourierLweBootstrapKey.serialize`` / ``deserialize``: the reference's
   bytes of the key (``fourier_bsk_format``)
@@ -278,7 +281,94 @@ def blind_rotate_assign(msed_input, lut, key: FourierLweBootstrapKey, ms_mode: i
                                             _stream(lut)))
 
 
+# ---- the multi-bit PBS (algorithms/lwe_multi_bit_programmable_bootstrapping.rs) ------------------------------------
+class FourierLweMultiBitBootstrapKey:
+    """A Fourier-domain multi-bit bootstrap key (n_lwe / g, 2^g, level, k+1, k+1, N/2, 2) float64, g =
+    ``grouping_factor`` (``mi_fft64_multi_bit_pbs_key``; the tensor is referenced, keep it alive).  GGSW ``idx`` of
+    group i encrypts prod_m (s[i g + m] XOR NOT bit_m(idx)) (lwe_multi_bit_bootstrap_key_generation.rs:398-421)."""
+
+    def __init__(self, fbsk, base_log: int, level: int, grouping_factor: int, fft: Fft | None = None):
+        g = int(grouping_factor)
+        if (fbsk.dim() != 7 or fbsk.shape[2] != level or fbsk.shape[-1] != 2 or fbsk.shape[3] != fbsk.shape[4]
+                or not 0 <= g < 31 or fbsk.shape[1] != 1 << g):
+            raise ValueError(f"assertion failed: fourier multi-bit bsk shape {tuple(fbsk.shape)} for grouping factor {g}")
+        n = 2 * int(fbsk.shape[-2])
+        self.fft = fft or Fft(n, fbsk.device.index or 0)
+        self.fbsk, self.base_log, self.level, self.grouping_factor = fbsk, base_log, level, g
+        self.input_lwe_dimension = int(fbsk.shape[0]) * g
+        self.glwe_dimension, self.polynomial_size = int(fbsk.shape[3]) - 1, n
+        h = ctypes.c_void_p()
+        check(lib().mi_fft64_multi_bit_pbs_key_create(self.fft.handle, _fdev(fbsk, "fbsk"), self.input_lwe_dimension,
+                                                      self.glwe_dimension, base_log, level, g, ctypes.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        release(self, "mi_fft64_multi_bit_pbs_key_destroy")
+
+    def output_lwe_size(self) -> int:
+        return self.glwe_dimension * self.polynomial_size + 1
+
+
+def convert_standard_lwe_multi_bit_bootstrap_key_to_fourier(input_bsk, output_bsk, fft: Fft | None = None) -> None:
+    """output_bsk (n_lwe / g, 2^g, level, k+1, k+1, N/2, 2) float64 = forward_as_torus of every polynomial of
+    input_bsk (n_lwe / g, 2^g, level, k+1, k+1, N) (lwe_multi_bit_bootstrap_key_conversion.rs)."""
+    convert_standard_lwe_bootstrap_key_to_fourier(input_bsk, output_bsk, fft)
+
+
+def _multi_bit_shapes(key, lwe_in, lwe_out):
+    batch = _lwe_batch(key, lwe_in)
+    if lwe_out.shape[-1] != key.output_lwe_size() or lwe_out.numel() // key.output_lwe_size() != batch:
+        raise ValueError(f"assertion failed: output lwe shape {tuple(lwe_out.shape)}")
+    return batch, (key.glwe_dimension + 1, key.polynomial_size)
+
+
+def multi_bit_programmable_bootstrap_lwe_ciphertext(lwe_in, lwe_out, accumulator, key: FourierLweMultiBitBootstrapKey,
+                                                    lut_index=None) -> None:
+    """Batched multi_bit_programmable_bootstrap_lwe_ciphertext (lwe_multi_bit_programmable_bootstrapping.rs:1029-1126)
+    of native-modulus LWEs, the deterministic rotation.  ``accumulator`` (k+1, N) is shared; with ``lut_index`` it is a
+    list (n_lut, k+1, N) as for ``programmable_bootstrap_lwe_ciphertext``."""
+    from .ntt64_pbs import _index
+    batch, glwe = _multi_bit_shapes(key, lwe_in, lwe_out)
+    if lut_index is None:
+        if tuple(accumulator.shape) != glwe:
+            raise ValueError(f"assertion failed: accumulator shape {tuple(accumulator.shape)}")
+        check(lib().mi_fft64_multi_bit_pbs_batch(key._h, _dev(lwe_out, "lwe_out"), _dev(lwe_in, "lwe_in"),
+                                                 _dev(accumulator, "accumulator"), batch, _stream(lwe_out)))
+        return
+    if accumulator.dim() != 3 or tuple(accumulator.shape[1:]) != glwe:
+        raise ValueError(f"assertion failed: accumulator list shape {tuple(accumulator.shape)} != (n_lut, *{glwe})")
+    check(lib().mi_fft64_multi_bit_pbs_batch_lut_indexed(key._h, _dev(lwe_out, "lwe_out"), _dev(lwe_in, "lwe_in"),
+                                                         _dev(accumulator, "accumulator"),
+                                                         _index(lut_index, batch, lwe_in.device, "lut_index"),
+                                                         int(accumulator.shape[0]), batch, _stream(lwe_out)))
+
+
+def batch_multi_bit_programmable_bootstrap_lwe_ciphertext(lwe_in, lwe_out, accumulators,
+                                                          key: FourierLweMultiBitBootstrapKey) -> None:
+    """One accumulator per input (``accumulators``: (batch, k+1, N))."""
+    batch, glwe = _multi_bit_shapes(key, lwe_in, lwe_out)
+    if accumulators.dim() != 3 or tuple(accumulators.shape) != (batch, *glwe):
+        raise ValueError(f"assertion failed: accumulator list shape {tuple(accumulators.shape)} != ({batch}, *{glwe})")
+    check(lib().mi_fft64_multi_bit_pbs_batch_lut_indexed(key._h, _dev(lwe_out, "lwe_out"), _dev(lwe_in, "lwe_in"),
+                                                         _dev(accumulators, "accumulators"), None, batch, batch,
+                                                         _stream(lwe_out)))
+
+
+def multi_bit_blind_rotate_assign(lwe_in, lut, key: FourierLweMultiBitBootstrapKey) -> None:
+    """multi_bit_blind_rotate_assign (lwe_multi_bit_programmable_bootstrapping.rs:366-410, 644-869), batched and in
+    place: lut (batch, k+1, N), every item rotated by its own native LWE (switched on the device)."""
+    batch = _lwe_batch(key, lwe_in)
+    glwe = (key.glwe_dimension + 1, key.polynomial_size)
+    if lut.dim() < 2 or tuple(lut.shape[-2:]) != glwe or lut.numel() != batch * glwe[0] * glwe[1]:
+        raise ValueError(f"assertion failed: lut shape {tuple(lut.shape)} != ({batch}, *{glwe})")
+    check(lib().mi_fft64_multi_bit_blind_rotate_batch(key._h, _dev(lut, "lut"), _dev(lwe_in, "lwe_in"), batch,
+                                                      _stream(lut)))
+
+
 __all__ = ["Fft", "FourierLweBootstrapKey", "convert_standard_lwe_bootstrap_key_to_fourier",
            "add_external_product_assign", "cmux_assign", "programmable_bootstrap_lwe_ciphertext",
            "batch_programmable_bootstrap_lwe_ciphertext", "blind_rotate_assign",
+           "FourierLweMultiBitBootstrapKey", "convert_standard_lwe_multi_bit_bootstrap_key_to_fourier",
+           "multi_bit_programmable_bootstrap_lwe_ciphertext", "batch_multi_bit_programmable_bootstrap_lwe_ciphertext",
+           "multi_bit_blind_rotate_assign",
            "MS_STANDARD", "MS_CENTERED", "MS_PRE_SWITCHED"]

@@ -635,6 +635,70 @@ int mi_glwe_compress_batch(uint64_t *packed, const uint64_t *glwe, size_t polyno
 int mi_glwe_extract_batch(uint64_t *glwe, const uint64_t *packed, size_t polynomial_size, int glwe_dim,
                           size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
 
+/* ---- The exact 128-bit programmable bootstrap (shortint noise squashing) -----------------------------------------
+ * programmable_bootstrap_f128_lwe_ciphertext (algorithms/lwe_programmable_bootstrapping/fft128_pbs.rs:174;
+ * fft_impl/fft128_u128/crypto/{bootstrap,ggsw}.rs) over Z_{2^128}[X]/(X^N + 1), as V1_4_NOISE_SQUASHING_PARAM_MESSAGE_2_
+ * CARRY_2_KS_PBS_TUNIFORM_2M128 runs it before threshold decryption (k = 2, N = 2048, base 2^24, 3 levels, native u128,
+ * centered modulus switch; shortint/parameters/v1_4/noise_squashing/p_fail_2_minus_128/mod.rs:8-19): the u64 LWE the
+ * keyswitch produces (dimension 918) is bootstrapped into a u128 LWE.  The reference multiplies with a double-double FFT;
+ * here the products run on the Goldilocks NTT and are exact: every u128 key coefficient is split into limbs of
+ * limb_bits bits, narrow enough that a whole column sum of digit x limb products stays below p / 2 and is read back as
+ * the integer it is.  The results are the reference's algorithm with its transform error removed: bit for bit the
+ * integer arithmetic mod 2^128 (SignedDecomposer<u128>, decomposer.rs:156-185 / collect_next_term_split_scalar,
+ * ggsw.rs:517-567; the exact negacyclic product).  Every u128 crosses this ABI as two little-endian u64 words (lo, hi),
+ * as mi_native_polymul_batch takes them; u128 buffers are 16-byte aligned device pointers.
+ * Not provided: non-native power-of-two moduli below 2^128 (the closest_representable step of blind_rotate_u128,
+ * bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the noise-squashing
+ * packing keyswitch (base_log 61 over u128), the C++ mirror, and the serialised Fourier128LweBootstrapKey format (it
+ * holds the output of the reference's own FFT and has no meaning here).
+ *
+ * mi_pbs128_limb_plan (no reference counterpart, needs no device): limb_bits = the largest w with
+ * R N 2^(base_log - 1) (2^w - 1) <= (p - 1) / 2, R = (k + 1) level, p = 2^64 - 2^32 + 1; n_limbs = ceil(128 / w)
+ * (w = 25, 6 limbs at the shape above).  MI_ERR_INVALID_ARG where SignedDecomposer::<u128>::new asserts (decomposer.rs:
+ * 86-90: base_log * level outside [1, 127]), for N not a power of two or above 2^31 and for k < 1 or above 65535, each
+ * with its own message;
+ * MI_ERR_UNSUPPORTED when n_limbs > 16 (the outputs are still written; both 0 when no width fits).  Either output may
+ * be NULL. */
+int mi_pbs128_limb_plan(size_t polynomial_size, int k, int base_log, int level, int *limb_bits, int *n_limbs);
+/* The bootstrap key.  bsk_std: the reference's LweBootstrapKey<u128> layout as a device pointer (n_ggsw GGSWs of
+ * `level` level matrices of (k + 1) GLWE rows of (k + 1) polynomials of polynomial_size u128, the level matrices in
+ * the order ggsw.into_levels() yields them, ggsw.rs:112-116, as the u64 keys).  A private prepared copy is made on
+ * `stream`, which is synchronised (the caller's buffer may be freed afterwards): limb polynomials through the plan's
+ * forward transform, N^-1 folded in, n_limbs x 8 bytes per coefficient, converted GGSW by GGSW straight into place (no
+ * second key-sized buffer).  `plan` must be the Goldilocks plan of polynomial_size (else MI_ERR_UNSUPPORTED), k <= 3;
+ * the argument rules and the limb bound of mi_pbs128_limb_plan apply.  The key borrows `plan` (its device and
+ * twiddle tables are read by every later call, mi_pbs128_key_destroy included): the plan must outlive the key; a plan
+ * from mi_ntt64_plan_cached always does. */
+typedef struct mi_pbs128_key mi_pbs128_key;
+int mi_pbs128_key_create(const mi_ntt64_plan *plan, const uint64_t *bsk_std, size_t n_ggsw, int k,
+                         size_t polynomial_size, int base_log, int level, void *stream, mi_pbs128_key **out_key);
+int mi_pbs128_key_destroy(mi_pbs128_key *key);
+int mi_pbs128_key_info(const mi_pbs128_key *key, size_t *n_ggsw, int *k, size_t *polynomial_size, int *base_log,
+                       int *level, int *limb_bits, int *n_limbs);
+/* add_external_product_assign_split (ggsw.rs:17): out_glwe[b] += GGSW (.) in_glwe[b] for `batch` GLWEs of
+ * (k + 1) polynomial_size u128, GGSW number ggsw_index of the key shared by the batch (an index >= n_ggsw is
+ * MI_ERR_INVALID_ARG and nothing is written).  cmux_split (ggsw.rs:621-675): ct1 -= ct0, then ct0 += GGSW (.) ct1;
+ * ct1 is left holding the difference, as the reference leaves it.  The two operands of a call are disjoint buffers
+ * (overlapping ones are MI_ERR_INVALID_ARG: the sum is written after the input was read by an earlier pass); so are
+ * the buffers of the two entries below.  Async on `stream`, stream-ordered scratch (at most
+ * ~4 GiB per chunk of the batch; the environment variable MI_PBS128_CHUNK, read per call, lowers the chunk's item
+ * count).  batch = 0 is MI_OK. */
+int mi_ext_product128_batch(const mi_pbs128_key *key, size_t ggsw_index, uint64_t *out_glwe, const uint64_t *in_glwe,
+                            size_t batch, void *stream);
+int mi_cmux128_batch(const mi_pbs128_key *key, size_t ggsw_index, uint64_t *ct0, uint64_t *ct1, size_t batch,
+                     void *stream);
+/* blind_rotate_assign_split (bootstrap.rs:60-150), batched and in place: acc_glwe[b] ((k + 1) polynomial_size u128) is
+ * divided by X^ms(body) and rotated through the CMUX loop over lwe_in[b] (n_ggsw + 1 u64 at the native 2^64 modulus;
+ * ms_mode as mi_pbs_ntt64_batch, log modulus log2(2N): switched on the device, or MI_MS_PRE_SWITCHED values in
+ * [0, 2N)).  A mask element that switches to 0 contributes exactly nothing, as the reference's skip. */
+int mi_blind_rotate128_batch(const mi_pbs128_key *key, uint64_t *acc_glwe, const uint64_t *lwe_in, size_t batch,
+                             int ms_mode, void *stream);
+/* programmable_bootstrap_f128_lwe_ciphertext / blind_rotate_u128 (bootstrap.rs:152-247) over a batch: the blind
+ * rotation of the one shared LUT GLWE `lut`, then extract_lwe_sample_from_glwe_ciphertext at degree 0:
+ * lwe_out[b] = k polynomial_size + 1 u128. */
+int mi_pbs128_batch(const mi_pbs128_key *key, uint64_t *lwe_out, const uint64_t *lwe_in, const uint64_t *lut,
+                    size_t batch, int ms_mode, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,5 +166,34 @@ hipError_t launch_pbs_tw_sol(uint64_t* out, const uint64_t* switched, const PbsI
 hipError_t launch_pbs_tw(uint64_t* out, const uint64_t* lwe_in, const PbsIo& io, const uint64_t* bsk, size_t n_lwe,
                          size_t batch, int base_log, const uint64_t* tab, int centered, hipStream_t s);
 
+// pbs128.hip — the exact 128-bit bootstrap over Z_{2^128}[X]/(X^N + 1) on the Goldilocks transform.  u128 buffers are
+// pairs of little-endian u64 words, 16-byte aligned.
+struct Pbs128Shape {
+  int logn = 0, k = 0, base_log = 0, level = 0, limb_bits = 0, n_limbs = 0;
+};
+// how the key's plan transforms (the routing of mi_ntt64_fwd_batch): the twisted N = 2048 body, the split transform, or
+// the register-window kernels; n_inv = N^-1 mod p
+struct Ntt128Route {
+  int logn = 0;
+  bool twisted = false, split = false;
+  const uint64_t *tw = nullptr, *itw = nullptr, *twist_f = nullptr, *twist_i = nullptr;
+  SplitTw st;
+  uint64_t n_inv = 0;
+};
+// u64 words of one prepared GGSW: level (k + 1)^2 n_limbs N
+size_t pbs128_ggsw_words(const Pbs128Shape& p);
+// dst = the prepared key of n_ggsw standard-domain u128 GGSWs: limb polynomials, forward transform, N^-1 folded in
+hipError_t launch_pbs128_key_prepare(uint64_t* dst, const uint64_t* src, size_t n_ggsw, const Pbs128Shape& p,
+                                     const Ntt128Route& rt, hipStream_t s);
+// out += GGSW (.) glwe; cmux: glwe -= out first (written back).  ggsw = one prepared GGSW, shared by the batch
+hipError_t launch_ext_product128(bool cmux, uint64_t* out, uint64_t* glwe, const uint64_t* ggsw, size_t batch,
+                                 const Pbs128Shape& p, const Ntt128Route& rt, hipStream_t s);
+// the blind rotation over n_lwe prepared GGSWs.  lut != NULL: every accumulator starts from the shared LUT and lwe_out
+// gets the extracted LWEs (k N + 1 u128); lut == NULL: acc_glwe is rotated in place.  lwe_in: u64 LWEs, switched here
+// (centered: with the body correction) or already switched (pre)
+hipError_t launch_blind_rotate128(uint64_t* lwe_out, uint64_t* acc_glwe, const uint64_t* lut, const uint64_t* lwe_in,
+                                  const uint64_t* key, size_t n_lwe, size_t batch, int centered, int pre,
+                                  const Pbs128Shape& p, const Ntt128Route& rt, hipStream_t s);
+
 }  // namespace mi
 // (keyswitch.hip's entry points: keyswitch_launch.hpp)

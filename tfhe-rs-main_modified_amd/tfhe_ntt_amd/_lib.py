@@ -162,6 +162,16 @@ _SIGS = {
     "mi_glwe_compressed_words": (_int, [_sz, _int, _sz, _int, ctypes.POINTER(_sz)]),
     "mi_glwe_compress_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
     "mi_glwe_extract_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
+    "mi_pbs128_limb_plan": (_int, [_sz, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "mi_pbs128_key_create": (_int, [_vp, _vp, _sz, _int, _sz, _int, _int, _vp, ctypes.POINTER(_vp)]),
+    "mi_pbs128_key_destroy": (_int, [_vp]),
+    "mi_pbs128_key_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_sz),
+                                  ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_int)]),
+    "mi_ext_product128_batch": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
+    "mi_cmux128_batch": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
+    "mi_blind_rotate128_batch": (_int, [_vp, _vp, _vp, _sz, _int, _vp]),
+    "mi_pbs128_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _vp]),
 }
 
 

@@ -39,17 +39,11 @@ struct mi_ntt64_plan {
   u64* d_twist_i = nullptr;
   u64* d_twist_fn = nullptr;  // forward twist rows x N^-1 + the forward lane-pair twiddles (normalising key conversion)
   // Solinas 2^12 <= N <= 2^MI_SPLIT_MAX_LOGN: the split transform (ntt64_kernels.hip launch_ntt_split): d_split holds
-  // the block twist alpha_b^j then alpha_b^-j (2 N u64); sub2048 is the cached 2048 plan whose body tables it uses
+  // the block twist alpha_b^j then alpha_b^-j (2 N u64); sub2048 is the cached 2048 plan whose body tables it uses;
+  // split = the four table pointers as the launchers take them, filled once when d_split is set
   u64* d_split = nullptr;
   const mi_ntt64_plan* sub2048 = nullptr;
-  mi::SplitTw split_tables() const {
-    mi::SplitTw t;
-    t.blk_fwd = d_split;
-    t.blk_inv = d_split + n;
-    t.body_fwd = sub2048->d_twist_f;
-    t.body_inv = sub2048->d_twist_i;
-    return t;
-  }
+  mi::SplitTw split;
 };
 
 struct mi_fft64_plan {
@@ -124,7 +118,15 @@ struct DeviceGuard {
   }
 };
 
-// shared by mi_pbs_ntt64_key_create and mi_pbs_ntt64_key_load
+// c_api.cpp, shared with the prime32 and native plans (c_api_native.cpp): the batch-argument checks of every
+// transform / pointwise entry, and the checked forward / inverse transform and pointwise op (0 normalize,
+// 1 mul_assign_normalize, 2 mul_accumulate) of a prime64 plan
+int check_batch(const mi_ntt64_plan* plan, const void* buf, size_t batch, size_t stride);
+int run_ntt(bool fwd, const mi_ntt64_plan* plan, uint64_t* buf, size_t batch, size_t stride, void* stream);
+int run_pw(int op, const mi_ntt64_plan* plan, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch,
+           size_t stride, void* stream);
+
+// c_api_pbs.cpp, shared by mi_pbs_ntt64_key_create and mi_pbs_ntt64_key_load
 int check_pbs_shape(const mi_ntt64_plan* plan, int k, int base_log, int level, int variant);
 // whether a consumer shape runs on the twisted N = 2048 engine (pbs_tw.hip: k = 1, level 1)
 bool twisted_ext_applies(const mi_ntt64_plan* plan, int variant, int k, int base_log, int level);

@@ -65,7 +65,7 @@ mi::Ntt128Route route_of(const mi_ntt64_plan* plan) {
   r.itw = plan->d_inv_twid;
   r.twist_f = plan->d_twist_f;
   r.twist_i = plan->d_twist_i;
-  if (r.split) r.st = plan->split_tables();
+  if (r.split) r.st = plan->split;
   r.n_inv = plan->n_inv;
   return r;
 }

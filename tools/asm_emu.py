@@ -524,7 +524,7 @@ def run_body(hdr, name, poly, twist_tab, fwd=True, out_of_place=False, mem_extra
 def _lds_with_lane_pair_tables(tab, N, stride=None):
     """Workgroup LDS as pbs_tw.hip lays it out: 2 exchange buffers of `stride` u64 (default N), then the 32 forward
     lane-pair twiddles (tab[N:N+32]) and the W1'' inverse's 32 last-DIT-stage twiddles, entry m + 16 par =
-    2^(-3 (2 m + par) mod 192) (the plan's fourth table region, c_api.cpp)."""
+    2^(-3 (2 m + par) mod 192) (the plan's fourth table region, ntt64_plan_tables.hpp twist_table)."""
     P = 0xFFFFFFFF00000001
     st = stride or N
     lds = np.zeros(2 * st + 64, dtype=np.uint64)

@@ -257,11 +257,24 @@ def test_generic_pbs_shortint_shapes_real_keys(engine, oracle, name):
         assert key3.serialize(True) == buf
 
 
+def _lanes_key(engine, n, g):
+    """A random Fourier key at the shape of the lane tests (k = 1, level 2, base 2^12, n_lwe = 3)."""
+    import torch
+    k, level, base_log, n_lwe = 1, 2, 12, 3
+    fft = engine.fft64.Fft(n)
+    bsk = H.uniform_u64(g, (n_lwe, level, k + 1, k + 1, n))
+    fbsk = torch.zeros((n_lwe, level, k + 1, k + 1, n // 2, 2), dtype=torch.float64, device="cuda")
+    engine.fft64.convert_standard_lwe_bootstrap_key_to_fourier(dev(bsk), fbsk, fft)
+    return engine.fft64.FourierLweBootstrapKey(fbsk, base_log, level, fft)
+
+
 @pytest.mark.parametrize("n", [4096, 8192])
 def test_generic_pbs_two_lanes(engine, n):
-    """A chunk of >= 64 ciphertexts runs as two lanes (halves on the caller's stream and a pooled side stream,
-    fft64_generic.hip FFTG_LANE_MIN): every output of an odd-split batch of 70 equals, bit for bit, the one-lane run
-    (batch 8 < 64) of the same items — each item's f64 arithmetic is independent of where the batch is cut."""
+    """A chunk of >= 64 ciphertexts runs as lanes (parts on the caller's stream and pooled side streams,
+    fft64_generic.hip): every output of an odd-split batch of 70 equals, bit for bit, the one-lane run (batch 8 < 64)
+    of the same items — each item's f64 arithmetic is independent of where the batch is cut.  N = 4096 runs two lanes
+    of 35; N = 8192 runs four by default, 18 / 18 / 17 / 17 items at offsets 0, 18, 36, 53, so its middle window
+    straddles the boundary at 36."""
     import torch
     k, level, base_log, n_lwe, batch = 1, 2, 12, 3, 70
     fft = engine.fft64.Fft(n)
@@ -275,9 +288,55 @@ def test_generic_pbs_two_lanes(engine, n):
     out = dev(np.zeros((batch, k * n + 1), np.uint64))
     engine.fft64.programmable_bootstrap_lwe_ciphertext(dev(lwe), out, dev(lut), key)
     got = host(out)
-    for lo in (0, 31, 62):  # the first half, across the split point (35), the second half
+    for lo in (0, 31, 62):  # the first lane, across a lane boundary (35 / 36), the last lane
         o8 = dev(np.zeros((8, k * n + 1), np.uint64))
         engine.fft64.programmable_bootstrap_lwe_ciphertext(dev(lwe[lo:lo + 8]), o8, dev(lut), key)
+        assert np.array_equal(host(o8), got[lo:lo + 8]), lo
+
+
+@pytest.mark.parametrize("n", [4096, 8192])
+def test_generic_blind_rotate_across_lanes(engine, n):
+    """The blind-rotate form (every item rotates its own GLWE in place) over the lanes of test_generic_pbs_two_lanes:
+    the same three windows equal, bit for bit, one-lane runs (batch 8) on copies of the same inputs."""
+    k, n_lwe, batch = 1, 3, 70
+    g = H.rng(8200 + n)
+    key = _lanes_key(engine, n, g)
+    luts = H.uniform_u64(g, (batch, k + 1, n))
+    lwe = H.uniform_u64(g, (batch, n_lwe + 1))
+    t = dev(luts)
+    engine.fft64.blind_rotate_assign(dev(lwe), t, key, engine.fft64.MS_STANDARD)
+    got = host(t)
+    assert not np.array_equal(got[batch - 1], luts[batch - 1])
+    for lo in (0, 31, 62):
+        t8 = dev(luts[lo:lo + 8])
+        engine.fft64.blind_rotate_assign(dev(lwe[lo:lo + 8]), t8, key, engine.fft64.MS_STANDARD)
+        assert np.array_equal(host(t8), got[lo:lo + 8]), lo
+
+
+@pytest.mark.parametrize("n", [4096, 8192])
+def test_generic_lut_index_across_lanes(engine, n):
+    """A LUT index per item over the same lanes, an out-of-range index in every lane at both N (items 5, 20, 40, 60):
+    the skipped rows keep the output's sentinel, and the same three windows equal the one-lane runs (batch 8) with the
+    matching index slices."""
+    import torch
+    k, n_lwe, batch, skipped = 1, 3, 70, (5, 20, 40, 60)
+    g = H.rng(8300 + n)
+    key = _lanes_key(engine, n, g)
+    luts = H.uniform_u64(g, (3, k + 1, n))
+    lwe = H.uniform_u64(g, (batch, n_lwe + 1))
+    idx = g.integers(0, 3, size=batch).astype(np.uint32)
+    idx[list(skipped)] = (3, 7, 3, 0xFFFFFFFF)
+    gi = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
+    sentinel = np.full((batch, k * n + 1), 0x5A5A5A5A5A5A5A5A, np.uint64)
+    out = dev(sentinel)
+    engine.fft64.programmable_bootstrap_lwe_ciphertext(dev(lwe), out, dev(luts), key, lut_index=gi(idx))
+    got = host(out)
+    for b in range(batch):
+        assert np.array_equal(got[b], sentinel[b]) == (b in skipped), b
+    for lo in (0, 31, 62):
+        o8 = dev(sentinel[:8])
+        engine.fft64.programmable_bootstrap_lwe_ciphertext(dev(lwe[lo:lo + 8]), o8, dev(luts), key,
+                                                           lut_index=gi(idx[lo:lo + 8]))
         assert np.array_equal(host(o8), got[lo:lo + 8]), lo
 
 

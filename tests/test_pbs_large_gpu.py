@@ -84,7 +84,7 @@ def test_large_random_keys(engine, oracle, n, bnf):
 @pytest.mark.parametrize("bnf", [True, False])
 def test_large_pbs_two_lanes(engine, oracle, bnf):
     """A chunk of >= 64 ciphertexts runs as two lanes (halves on the caller's stream and a pooled side stream, their
-    launches interleaved per CMUX step; pbs_large.hip PBS_LANE_MIN): every output of an odd-split batch of 70 equals
+    launches interleaved per CMUX step; pbs_passes.hpp lanes_wanted): every output of an odd-split batch of 70 equals
     the one-lane run (batch 8 < 64) of the same items, and an item of each half equals the oracle bit for bit."""
     n, k, base_log, level, n_lwe, batch = 8192, 1, 15, 2, 3, 70
     q = 0 if bnf else P
@@ -108,6 +108,65 @@ def test_large_pbs_two_lanes(engine, oracle, bnf):
     for b in (0, batch - 1):
         want = c.pbs(lwe[b], lut.reshape(-1), bsk.reshape(-1), k, base_log, level, bnf=bnf)
         assert np.array_equal(got[b], want), b
+
+
+def _two_lane_case(engine, bnf, seed):
+    """The shape of test_large_pbs_two_lanes (70 items = two lanes of 35) on a random key: (module, key, rng, q)."""
+    n, k, base_log, level, n_lwe = 8192, 1, 15, 2, 3
+    M = engine.ntt64_pbs
+    g = H.rng(seed + bnf)
+    bsk = rand_q(g, (n_lwe, level, k + 1, k + 1, n), P)
+    key = M.NttBootstrapKey(engine.Plan.try_new(n, P), dev(bsk), base_log, level, M.BNF if bnf else M.SOLINAS)
+    return M, key, g, 0 if bnf else P
+
+
+@pytest.mark.parametrize("bnf", [True, False])
+def test_large_blind_rotate_across_lanes(engine, bnf):
+    """The blind-rotate form (every item rotates its own GLWE in place, PbsIo per_item + glwe_out) over two lanes of
+    35: the rows of the first lane, across the lane boundary (35) and of the second lane equal, bit for bit, one-lane
+    runs (batch 8 < 64) on copies of the same inputs.  The one-lane large path is anchored to the oracle at N = 16384
+    in test_blind_rotate_gpu.py."""
+    n, k, n_lwe, batch = 8192, 1, 3, 70
+    M, key, g, q = _two_lane_case(engine, bnf, 1310)
+    fn = M.blind_rotate_ntt64_bnf_assign if bnf else M.blind_rotate_ntt64_assign
+    luts = rand_q(g, (batch, k + 1, n), q)
+    lwe = rand_q(g, (batch, n_lwe + 1), q)
+    t = dev(luts)
+    fn(dev(lwe), t, key, M.MS_STANDARD)
+    got = host(t)
+    assert not np.array_equal(got[batch - 1], luts[batch - 1])
+    for lo in (0, 31, 62):
+        t8 = dev(luts[lo:lo + 8])
+        fn(dev(lwe[lo:lo + 8]), t8, key, M.MS_STANDARD)
+        assert np.array_equal(host(t8), got[lo:lo + 8]), lo
+
+
+@pytest.mark.parametrize("bnf", [True, False])
+def test_large_lut_index_across_lanes(engine, bnf):
+    """A LUT index per item over two lanes of 35, one out-of-range index in each lane (items 5 and 40): the two
+    skipped rows keep the output's sentinel, and the same three windows equal the one-lane runs (batch 8) with the
+    matching index slices."""
+    import torch
+    n, k, n_lwe, batch = 8192, 1, 3, 70
+    M, key, g, q = _two_lane_case(engine, bnf, 1320)
+    fn = (M.programmable_bootstrap_ntt64_bnf_lwe_ciphertext_mem_optimized if bnf else
+          M.programmable_bootstrap_ntt64_lwe_ciphertext_mem_optimized)
+    luts = rand_q(g, (3, k + 1, n), q)
+    lwe = rand_q(g, (batch, n_lwe + 1), q)
+    idx = g.integers(0, 3, size=batch).astype(np.uint32)
+    idx[5], idx[40] = 3, 7
+    assert len(set(idx[:35].tolist())) == 4 and len(set(idx[35:].tolist())) == 4  # every LUT in both lanes
+    gi = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
+    sentinel = np.full((batch, k * n + 1), 0x5A5A5A5A5A5A5A5A, np.uint64)
+    o = dev(sentinel)
+    fn(dev(lwe), o, dev(luts), key, lut_index=gi(idx))
+    got = host(o)
+    for b in range(batch):
+        assert np.array_equal(got[b], sentinel[b]) == (b in (5, 40)), b
+    for lo in (0, 31, 62):
+        o8 = dev(sentinel[:8])
+        fn(dev(lwe[lo:lo + 8]), o8, dev(luts), key, lut_index=gi(idx[lo:lo + 8]))
+        assert np.array_equal(host(o8), got[lo:lo + 8]), lo
 
 
 @pytest.mark.parametrize("bnf", [True, False])

@@ -34,11 +34,11 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "scratch.hpp"
 #include "fft64_device.hpp"
 #include "fft64_launch.hpp"
+#include "pbs_passes.hpp"
 
 namespace mi {
 namespace fft {
@@ -359,15 +359,13 @@ __global__ __launch_bounds__(RowGeom<LOGC>::T) void rows_kernel(Src src, Dst dst
 }
 
 // ---- column pass (R > 1): radix-R DFT over n1 of x[n1 C + n2], four-step twiddle W_M^(n2 k1) ----------------
-__device__ __forceinline__ uint64_t gs_start() { return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ uint64_t gs_stride() { return (uint64_t)gridDim.x * blockDim.x; }
 
 template <int LOGR, class Src>
 __global__ __launch_bounds__(256) void cols_fwd_kernel(Src src, cplx* __restrict__ out, uint64_t polys, uint32_t logc,
                                                        const cplx* __restrict__ wm) {
   constexpr int R = 1 << LOGR;
   const uint32_t cmask = (1u << logc) - 1u;
-  for (uint64_t i = gs_start(); i < (polys << logc); i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < (polys << logc); i += grid_stride()) {
     const uint64_t p = i >> logc;
     const uint32_t n2 = (uint32_t)i & cmask;
     cplx a[R];
@@ -388,7 +386,7 @@ __global__ __launch_bounds__(256) void cols_inv_kernel(Sink sink, const cplx* __
                                                        uint32_t logc, const cplx* __restrict__ wm) {
   constexpr int R = 1 << LOGR;
   const uint32_t cmask = (1u << logc) - 1u;
-  for (uint64_t i = gs_start(); i < (polys << logc); i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < (polys << logc); i += grid_stride()) {
     const uint64_t p = i >> logc;
     const uint32_t n2 = (uint32_t)i & cmask;
     const cplx* src = in + (p << (logc + LOGR));
@@ -415,14 +413,14 @@ __host__ __device__ __forceinline__ uint32_t frequency_at(uint32_t pos, uint32_t
 
 // the in-place reorder's staging copy (a kernel, not an SDMA copy: ordered on the stream like every other launch)
 __global__ __launch_bounds__(256) void copy_cplx_kernel(cplx* __restrict__ out, const cplx* __restrict__ in, uint64_t n) {
-  for (uint64_t i = gs_start(); i < n; i += gs_stride()) out[i] = in[i];
+  for (uint64_t i = grid_stride_start(); i < n; i += grid_stride()) out[i] = in[i];
 }
 
 template <bool TO_STD>
 __global__ __launch_bounds__(256) void reorder_kernel(cplx* __restrict__ out, const cplx* __restrict__ in,
                                                       uint64_t polys, uint32_t logc, uint32_t logr) {
   const uint32_t logm = logc + logr, mmask = (1u << logm) - 1u;
-  for (uint64_t i = gs_start(); i < (polys << logm); i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < (polys << logm); i += grid_stride()) {
     const uint64_t base = i & ~(uint64_t)mmask;
     const uint32_t j = (uint32_t)i & mmask;
     out[i] = in[base + (TO_STD ? position_of(j, logc, logr) : frequency_at(j, logc, logr))];
@@ -439,7 +437,7 @@ __global__ __launch_bounds__(256) void init_acc_kernel(u64* __restrict__ acc, Pb
                                                        int ms_mode) {
   const uint32_t nn = 1u << logn;
   const uint64_t per = (uint64_t)kp1 << logn;
-  for (uint64_t i = gs_start(); i < per * batch; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < per * batch; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     const uint32_t c = (uint32_t)(ce >> logn), m = (uint32_t)ce & (nn - 1);
     const u64* lut = io.lut_for(b0 + b, per);
@@ -456,22 +454,13 @@ __global__ __launch_bounds__(256) void init_acc_kernel(u64* __restrict__ acc, Pb
   }
 }
 
-// centered_binary_ms_body_correction_to_add (algorithms/modulus_switch.rs:60-104), one workgroup per ciphertext
-__global__ __launch_bounds__(256) void body_correction_kernel(u64* __restrict__ corr, const u64* __restrict__ lwe,
-                                                              uint32_t n_lwe, unsigned log_mod) {
-  __shared__ u64 sh[512];
-  const u64 v = centered_body_correction<256>(lwe + (uint64_t)blockIdx.x * (n_lwe + 1), n_lwe, log_mod,
-                                              (int)threadIdx.x, sh);
-  if (threadIdx.x == 0) corr[blockIdx.x] = v;
-}
-
 // extract_lwe_sample_from_glwe_ciphertext, nth = 0: out[c N] = A_c[0], out[c N + j] = -A_c[N - j], out[k N] = B[0];
 // items whose LUT index is out of range (io.lut_idx) are not written
 __global__ __launch_bounds__(256) void extract_kernel(u64* __restrict__ out, const u64* __restrict__ acc,
                                                       uint32_t batch, uint32_t logn, uint32_t k, PbsIo io, uint64_t b0) {
   const uint32_t nn = 1u << logn;
   const uint64_t per_out = ((uint64_t)k << logn) + 1, per = (uint64_t)(k + 1) << logn;
-  for (uint64_t i = gs_start(); i < per_out * batch; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < per_out * batch; i += grid_stride()) {
     const uint64_t b = i / per_out, o = i % per_out;
     if (io.lut_idx && !io.lut_for(b0 + b, per)) continue;
     const uint32_t c = (uint32_t)(o >> logn), j = (uint32_t)o & (nn - 1);
@@ -483,7 +472,7 @@ __global__ __launch_bounds__(256) void extract_kernel(u64* __restrict__ out, con
 // blind_rotate_assign (fft64_pbs.rs:186-250): the rotated accumulators of a chunk into io.glwe_out (skipped items kept)
 __global__ __launch_bounds__(256) void store_glwe_kernel(const u64* __restrict__ acc, uint32_t batch, uint64_t per,
                                                          PbsIo io, uint64_t b0) {
-  for (uint64_t i = gs_start(); i < per * batch; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < per * batch; i += grid_stride()) {
     const uint64_t b = i / per;
     if (!io.lut_for(b0 + b, per)) continue;
     io.glwe_out[b0 * per + i] = acc[i];
@@ -492,10 +481,8 @@ __global__ __launch_bounds__(256) void store_glwe_kernel(const u64* __restrict__
 
 // CMUX input: ct1 -= ct0 (cmux, fft64_pbs.rs:510-560), elementwise
 __global__ __launch_bounds__(256) void sub_assign_kernel(u64* __restrict__ a, const u64* __restrict__ b, uint64_t count) {
-  for (uint64_t i = gs_start(); i < count; i += gs_stride()) a[i] -= b[i];
+  for (uint64_t i = grid_stride_start(); i < count; i += grid_stride()) a[i] -= b[i];
 }
-
-inline unsigned blocks_for(uint64_t total) { return (unsigned)std::min<uint64_t>((total + 255) / 256, 65536); }
 
 // ---- launch helpers ---------------------------------------------------------------------------------------
 template <int LOGC, bool INV, class Src, class Dst>
@@ -587,11 +574,10 @@ hipError_t inverse(const Geo& g, Src src, Sink sink, cplx* tmp, uint64_t polys, 
   return cols_inv(g.logr, sink, tmp, polys, g.logc, g.wm, s);
 }
 
-// items per chunk: digits (level (k + 1) M complex), products (R > 1: (k + 1) M complex) and accumulators stay
-// below ~4 GiB of scratch (of 288 GB)
-inline size_t chunk_for(const Geo& g, uint32_t kp1, uint32_t level, size_t batch) {
-  const size_t per_item = ((size_t)level + 2) * kp1 * ((size_t)8 << g.logn);
-  return std::max<size_t>(1, std::min(batch, ((size_t)4 << 30) / per_item));
+// scratch of one chunk item: digits (level (k + 1) M complex), products (R > 1: (k + 1) M complex) and accumulator
+// (the chunk size of chunk_items)
+inline size_t item_bytes(const Geo& g, uint32_t kp1, uint32_t level) {
+  return ((size_t)level + 2) * kp1 * ((size_t)8 << g.logn);
 }
 
 }  // namespace gen
@@ -669,7 +655,7 @@ hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* gl
   const Geo g = geo(t);
   const uint32_t kp1 = (uint32_t)k + 1, lv = (uint32_t)level;
   const size_t per = (size_t)kp1 << g.logn;  // u64 per GLWE
-  const size_t chunk = chunk_for(g, kp1, lv, batch);
+  const size_t chunk = chunk_items(item_bytes(g, kp1, lv), batch);
   const size_t dig = ((chunk * lv * kp1) << g.logm), prod = g.logr ? ((chunk * kp1) << g.logm) : 0;
   cplx* scratch = nullptr;
   hipError_t e = mi::scratch_alloc((void**)&scratch, (dig + prod) * sizeof(cplx), s);
@@ -694,15 +680,12 @@ hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* gl
   return e != hipSuccess ? e : ef;
 }
 
-// Lanes, as launch_pbs_large (pbs_large.hip): a chunk of >= FFTG_LANE_MIN ciphertexts is split into
-// mi::pbs_lane_count(fftg_default_lanes(logn)) parts on the caller's stream and pooled side streams (mi::StreamFork), launches interleaved step
-// by step, so one part's memory-bound passes overlap another's transform rows.
-static constexpr uint32_t FFTG_LANE_MIN = 64;
+// The chunk loop and the lanes are run_blind_rotation's (pbs_passes.hpp), as launch_pbs_large's: one lane's
+// memory-bound passes overlap another's transform rows.
 // default lane count per N, from the one-box sweep of profiles/r4/session24/lane_sweep.txt (PBS/s at 1 / 2 / 3 / 4
 // lanes: 1_1 (N 512) 35.6 / 41.9 / 41.4 / 34.8 k, 3_3 (N 8192) 2.36 / 2.55 / 2.53 / 2.67 k, 4_4 (N 65536) 176 / 184 /
 // 187 / 181) and the next boxes (4_4: 184.4 at 2 lanes, 180.1 at 3; 3_3: 2.67 k at 4 again, profiles/r4/session27/)
 static int fftg_default_lanes(uint32_t logn) { return logn >= 16 ? 2 : logn >= 13 ? 4 : 2; }
-
 
 hipError_t launch_fftg_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const PbsIo& io, const double* fbsk,
                            size_t n_lwe, size_t batch, int base_log, int level, int ms_mode, const FftGenTables& t,
@@ -712,7 +695,7 @@ hipError_t launch_fftg_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const P
   const Geo g = geo(t);
   const uint32_t kp1 = (uint32_t)k + 1, lv = (uint32_t)level;
   const size_t per = (size_t)kp1 << g.logn;
-  const size_t chunk = chunk_for(g, kp1, lv, batch);
+  const size_t chunk = chunk_items(item_bytes(g, kp1, lv), batch);
   const size_t dig = ((chunk * lv * kp1) << g.logm), prod = g.logr ? ((chunk * kp1) << g.logm) : 0;
   const size_t acc_u64 = chunk * per;
   cplx* scratch = nullptr;
@@ -724,63 +707,48 @@ hipError_t launch_fftg_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const P
   uint64_t* corr_all = acc_all + acc_u64;
   const cplx* key = reinterpret_cast<const cplx*>(fbsk);
   const size_t ggsw_len = ((size_t)lv * kp1 * kp1) << g.logm;  // complex per GGSW
-  struct Lane {  // ciphertexts [b0, b0 + nb) of the batch, their scratch slices, their stream
-    size_t b0;
-    uint32_t nb;
-    hipStream_t st;
+  struct Part {  // a lane's inputs and its slices of the chunk's scratch (from its L.off)
     const uint64_t* in;
     cplx *d, *y;
     uint64_t *acc, *corr;
   };
-  for (size_t c0 = 0; c0 < batch && e == hipSuccess; c0 += chunk) {
-    const uint32_t nb_all = (uint32_t)std::min(chunk, batch - c0);
-    mi::StreamFork fork;
-    const int want = nb_all >= FFTG_LANE_MIN ? std::min<int>(mi::pbs_lane_count(fftg_default_lanes(g.logn)), (int)(nb_all / 16)) : 1;
-    if (want > 1) (void)fork.fork(s, want - 1);  // fewer lanes when a side stream cannot be had
-    const int lanes = 1 + fork.sides();
-    Lane L[1 + mi::StreamFork::MAX_SIDE];
-    for (int j = 0, off = 0; j < lanes; ++j) {
-      const uint32_t n = nb_all / lanes + ((uint32_t)j < nb_all % lanes ? 1u : 0u);
-      L[j] = Lane{c0 + off, n, j == 0 ? s : fork.side(j - 1), lwe_in + (c0 + off) * (n_lwe + 1),
-                  d_all + (((size_t)off * lv * kp1) << g.logm), y_all ? y_all + (((size_t)off * kp1) << g.logm) : nullptr,
-                  acc_all + (size_t)off * per, corr_all + off};
-      off += (int)n;
+  auto part = [&](const Lane& L) {
+    return Part{lwe_in + L.b0 * (n_lwe + 1), d_all + (((size_t)L.off * lv * kp1) << g.logm),
+                y_all ? y_all + (((size_t)L.off * kp1) << g.logm) : nullptr, acc_all + (size_t)L.off * per,
+                corr_all + L.off};
+  };
+  auto init = [&](const Lane& L) -> hipError_t {
+    const Part p = part(L);
+    const hipError_t e =
+        ms_mode == 1 ? launch_body_correction(p.corr, p.in, (uint32_t)n_lwe, g.logn + 1, L.nb, L.st) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(init_acc_kernel, dim3(blocks_for((uint64_t)L.nb * per)), dim3(256), 0, L.st, p.acc, io,
+                       (uint64_t)L.b0, p.in, ms_mode == 1 ? (const uint64_t*)p.corr : nullptr, (uint32_t)n_lwe, L.nb,
+                       g.logn, kp1, ms_mode);
+    return hipGetLastError();
+  };
+  auto step = [&](const Lane& L, uint32_t i) -> hipError_t {
+    const Part p = part(L);
+    const hipError_t e =
+        forward(g, RotDigitSrc{p.acc, p.in, g.tw, g.logn, kp1, lv, (uint32_t)n_lwe, i, base_log, ms_mode}, p.d,
+                (uint64_t)L.nb * lv * kp1, L.st);
+    if (e != hipSuccess) return e;
+    return inverse(g, MacSrc{p.d, key + i * ggsw_len, g.logm, g.logc, g.logr, kp1, lv}, AccSink{p.acc, g.untw, g.logn},
+                   p.y, (uint64_t)L.nb * kp1, L.st);
+  };
+  auto finish = [&](const Lane& L) -> hipError_t {  // outputs are indexed by the lane's global b0
+    const Part p = part(L);
+    if (io.glwe_out) {
+      hipLaunchKernelGGL(store_glwe_kernel, dim3(blocks_for((uint64_t)L.nb * per)), dim3(256), 0, L.st,
+                         (const uint64_t*)p.acc, L.nb, (uint64_t)per, io, (uint64_t)L.b0);
+    } else {
+      const uint64_t per_out = ((uint64_t)k << g.logn) + 1;
+      hipLaunchKernelGGL(extract_kernel, dim3(blocks_for(L.nb * per_out)), dim3(256), 0, L.st, out + L.b0 * per_out,
+                         (const uint64_t*)p.acc, L.nb, g.logn, (uint32_t)k, io, (uint64_t)L.b0);
     }
-    for (int j = 0; j < lanes && e == hipSuccess; ++j) {
-      const Lane& l = L[j];
-      if (ms_mode == 1)
-        hipLaunchKernelGGL(body_correction_kernel, dim3(l.nb), dim3(256), 0, l.st, l.corr, l.in, (uint32_t)n_lwe,
-                           g.logn + 1);
-      hipLaunchKernelGGL(init_acc_kernel, dim3(blocks_for((uint64_t)l.nb * per)), dim3(256), 0, l.st, l.acc, io,
-                         (uint64_t)l.b0, l.in, ms_mode == 1 ? (const uint64_t*)l.corr : nullptr, (uint32_t)n_lwe, l.nb,
-                         g.logn, kp1, ms_mode);
-      e = hipGetLastError();
-    }
-    for (uint32_t i = 0; i < (uint32_t)n_lwe && e == hipSuccess; ++i)
-      for (int j = 0; j < lanes && e == hipSuccess; ++j) {
-        const Lane& l = L[j];
-        e = forward(g, RotDigitSrc{l.acc, l.in, g.tw, g.logn, kp1, lv, (uint32_t)n_lwe, i, base_log, ms_mode}, l.d,
-                    (uint64_t)l.nb * lv * kp1, l.st);
-        if (e == hipSuccess)
-          e = inverse(g, MacSrc{l.d, key + i * ggsw_len, g.logm, g.logc, g.logr, kp1, lv},
-                      AccSink{l.acc, g.untw, g.logn}, l.y, (uint64_t)l.nb * kp1, l.st);
-      }
-    for (int j = 0; j < lanes && e == hipSuccess; ++j) {
-      const Lane& l = L[j];
-      if (io.glwe_out) {
-        hipLaunchKernelGGL(store_glwe_kernel, dim3(blocks_for((uint64_t)l.nb * per)), dim3(256), 0, l.st,
-                           (const uint64_t*)l.acc, l.nb, (uint64_t)per, io, (uint64_t)l.b0);
-      } else {
-        const uint64_t outs = (uint64_t)l.nb * (((uint64_t)k << g.logn) + 1);
-        hipLaunchKernelGGL(extract_kernel, dim3(blocks_for(outs)), dim3(256), 0, l.st,
-                           out + l.b0 * (((size_t)k << g.logn) + 1), (const uint64_t*)l.acc, l.nb, g.logn,
-                           (uint32_t)k, io, (uint64_t)l.b0);
-      }
-      e = hipGetLastError();
-    }
-    const hipError_t ej = fork.join();  // the caller's stream after the side lane (also on error: scratch ordering)
-    if (e == hipSuccess) e = ej;
-  }
+    return hipGetLastError();
+  };
+  e = run_blind_rotation(batch, chunk, (uint32_t)n_lwe, fftg_default_lanes(g.logn), s, init, step, finish);
   const hipError_t ef = mi::scratch_free(scratch, s);
   return e != hipSuccess ? e : ef;
 }

@@ -41,6 +41,7 @@
 #include "mi_arith.hpp"
 #include "ntt64_launch.hpp"
 #include "pbs_device.hpp"
+#include "pbs_passes.hpp"
 
 namespace mi {
 namespace pbs128 {
@@ -54,9 +55,6 @@ struct Shape {
   uint32_t logn, n, k, level, limb_bits, n_limbs;
   int base_log;
 };
-
-__device__ __forceinline__ uint64_t gs_start() { return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ uint64_t gs_stride() { return (uint64_t)gridDim.x * blockDim.x; }
 
 // u128 values are two little-endian u64 words (lo, hi), 16-byte aligned: element i at p + 2 i
 __device__ __forceinline__ u128 ld128(const u64* p, uint64_t i) {
@@ -112,7 +110,7 @@ __device__ __forceinline__ uint32_t switched(u64 raw, unsigned log_mod, int pre)
 __global__ __launch_bounds__(256) void split_key(u64* __restrict__ dst, const u64* __restrict__ src, uint64_t count,
                                                  Shape sh) {
   const u64 mask = ((u64)1 << sh.limb_bits) - 1;
-  for (uint64_t i = gs_start(); i < count; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < count; i += grid_stride()) {
     const uint64_t poly = i >> sh.logn, e = i & (sh.n - 1);
     const u128 g = ld128(src, i);
     u64* o = dst + ((poly * sh.n_limbs) << sh.logn) + e;
@@ -126,7 +124,7 @@ template <bool CMUX>
 __global__ __launch_bounds__(256) void glwe_decompose(u64* __restrict__ digits, u64* __restrict__ glwe,
                                                       const u64* __restrict__ out, uint32_t batch, Shape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, total = per * batch;
-  for (uint64_t i = gs_start(); i < total; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     u128 x = ld128(glwe, i);
     if (CMUX) {
@@ -137,22 +135,13 @@ __global__ __launch_bounds__(256) void glwe_decompose(u64* __restrict__ digits, 
   }
 }
 
-// centered_binary_ms_body_correction_to_add (algorithms/modulus_switch.rs:60-104), one workgroup per ciphertext
-__global__ __launch_bounds__(256) void body_correction(u64* __restrict__ corr, const u64* __restrict__ lwe_in,
-                                                       uint32_t n_lwe, unsigned log_mod) {
-  __shared__ u64 sh[512];
-  const u64 v = pbs::centered_body_correction<256>(lwe_in + (uint64_t)blockIdx.x * (n_lwe + 1), n_lwe, log_mod,
-                                                   (int)threadIdx.x, sh);
-  if (threadIdx.x == 0) corr[blockIdx.x] = v;
-}
-
 // acc[b] = src / X^ms(body) (polynomial_wrapping_monic_monomial_div_assign_split, bootstrap.rs:82-91): new[m] =
 // old[(m + rem) % N], negated for m >= N - rem; src = the shared LUT (src_stride 0) or the item's own accumulator
 __global__ __launch_bounds__(256) void init_acc(u64* __restrict__ acc, const u64* __restrict__ src, uint64_t src_stride,
                                                 const u64* __restrict__ lwe_in, const u64* __restrict__ corr,
                                                 uint32_t n_lwe, int pre, uint32_t batch, Shape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, total = per * batch;
-  for (uint64_t i = gs_start(); i < total; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     const uint32_t c = (uint32_t)(ce >> sh.logn), m = (uint32_t)(ce & (sh.n - 1));
     const u64 raw = lwe_in[b * (n_lwe + 1) + n_lwe] + (corr ? corr[b] : 0);
@@ -170,7 +159,7 @@ __global__ __launch_bounds__(256) void rotate_decompose(u64* __restrict__ digits
                                                         const u64* __restrict__ lwe_in, uint32_t n_lwe, uint32_t step,
                                                         int pre, uint32_t batch, Shape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, total = per * batch;
-  for (uint64_t i = gs_start(); i < total; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     const uint32_t e = (uint32_t)(ce & (sh.n - 1));
     const uint32_t a = switched(lwe_in[b * (n_lwe + 1) + step], sh.logn + 1, pre);
@@ -235,7 +224,7 @@ __global__ __launch_bounds__(256) void mac(u64* __restrict__ y, const u64* __res
 __global__ __launch_bounds__(256) void recombine(u64* __restrict__ out, const u64* __restrict__ y, uint32_t batch,
                                                  Shape sh) {
   const uint64_t total = (uint64_t)(sh.k + 1) * sh.n * batch;
-  for (uint64_t i = gs_start(); i < total; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t poly = i >> sh.logn, e = i & (sh.n - 1);
     const u64* v = y + ((poly * sh.n_limbs) << sh.logn) + e;
     u64x2 acc = *reinterpret_cast<const u64x2*>(out + 2 * i);
@@ -267,16 +256,12 @@ __global__ __launch_bounds__(256) void recombine(u64* __restrict__ out, const u6
 __global__ __launch_bounds__(256) void extract(u64* __restrict__ lwe_out, const u64* __restrict__ acc, uint32_t batch,
                                                Shape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, per_out = (uint64_t)sh.k * sh.n + 1, total = per_out * batch;
-  for (uint64_t i = gs_start(); i < total; i += gs_stride()) {
+  for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per_out, o = i % per_out;
     const uint32_t c = (uint32_t)(o >> sh.logn), j = (uint32_t)(o & (sh.n - 1));  // o = k N gives c = k, j = 0
     const u128 v = ld128(acc, b * per + (uint64_t)c * sh.n + (j == 0 ? 0 : sh.n - j));
     st128(lwe_out, i, j == 0 ? v : (u128)0 - v);
   }
-}
-
-inline unsigned blocks_for(uint64_t total) {
-  return (unsigned)std::min<uint64_t>((total + 255) / 256, 65536);
 }
 
 inline Shape shape_of(const Pbs128Shape& p) {
@@ -322,15 +307,15 @@ inline size_t item_words(const Shape& sh, bool rotation) {
   return per * sh.level + per * sh.n_limbs + (rotation ? 2 * per + 1 : 0);
 }
 
-// ciphertexts per chunk: one chunk's scratch stays below ~4 GiB (as pbs_large.hip chunk_for).  MI_PBS128_CHUNK, read
-// on every call, lowers the bound (the tests force two chunks with it)
-inline size_t chunk_for(const Shape& sh, size_t batch, bool rotation) {
-  size_t chunk = std::max<size_t>(1, ((size_t)4 << 30) / (item_words(sh, rotation) * sizeof(u64)));
+// ciphertexts per chunk: chunk_items of the item's scratch.  MI_PBS128_CHUNK, read on every call, lowers the bound (the
+// tests force two chunks with it)
+inline size_t chunk_size(const Shape& sh, size_t batch, bool rotation) {
+  size_t chunk = chunk_items(item_words(sh, rotation) * sizeof(u64), batch);
   if (const char* v = std::getenv("MI_PBS128_CHUNK")) {
     const long long c = std::atoll(v);
     if (c >= 1) chunk = std::min<size_t>(chunk, (size_t)c);
   }
-  return std::min(batch, chunk);
+  return chunk;
 }
 
 // transform, mac, inverse, recombine of `nb` items whose digits are written: out += GGSW (.) (the decomposed input)
@@ -374,7 +359,7 @@ hipError_t launch_ext_product128(bool cmux, uint64_t* out, uint64_t* glwe, const
   using namespace pbs128;
   if (batch == 0) return hipSuccess;
   const Shape sh = shape_of(p);
-  const size_t per = (size_t)(p.k + 1) * sh.n, chunk = chunk_for(sh, batch, false);
+  const size_t per = (size_t)(p.k + 1) * sh.n, chunk = chunk_size(sh, batch, false);
   u64* scratch = nullptr;
   hipError_t e = mi::scratch_alloc((void**)&scratch, chunk * item_words(sh, false) * sizeof(u64), s);
   if (e != hipSuccess) return e;
@@ -400,7 +385,7 @@ hipError_t launch_blind_rotate128(uint64_t* lwe_out, uint64_t* acc_glwe, const u
   using namespace pbs128;
   if (batch == 0) return hipSuccess;
   const Shape sh = shape_of(p);
-  const size_t per = (size_t)(p.k + 1) * sh.n, chunk = chunk_for(sh, batch, true);
+  const size_t per = (size_t)(p.k + 1) * sh.n, chunk = chunk_size(sh, batch, true);
   const size_t ggsw_words = pbs128_ggsw_words(p), per_out = (size_t)p.k * sh.n + 1;
   u64* scratch = nullptr;
   hipError_t e = mi::scratch_alloc((void**)&scratch, chunk * item_words(sh, true) * sizeof(u64), s);
@@ -409,31 +394,32 @@ hipError_t launch_blind_rotate128(uint64_t* lwe_out, uint64_t* acc_glwe, const u
   u64* digits = acc + chunk * 2 * per;
   u64* y = digits + chunk * sh.level * per;
   u64* corr = y + chunk * sh.n_limbs * per;
-  for (size_t b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-    const uint32_t nb = (uint32_t)std::min(chunk, batch - b0);
-    const u64* in = lwe_in + b0 * (n_lwe + 1);
-    const dim3 grid(blocks_for((uint64_t)nb * per));
-    if (centered)
-      hipLaunchKernelGGL(body_correction, dim3(nb), dim3(256), 0, s, corr, in, (uint32_t)n_lwe,
-                         (unsigned)(p.logn + 1));
-    const u64* src = lut ? lut : acc_glwe + 2 * b0 * per;
-    hipLaunchKernelGGL(init_acc, grid, dim3(256), 0, s, acc, src, (uint64_t)(lut ? 0 : per), in,
-                       centered ? corr : (const u64*)nullptr, (uint32_t)n_lwe, pre, nb, sh);
-    e = hipGetLastError();
-    for (uint32_t i = 0; i < n_lwe && e == hipSuccess; ++i) {
-      hipLaunchKernelGGL(rotate_decompose, grid, dim3(256), 0, s, digits, acc, in, (uint32_t)n_lwe, i, pre, nb, sh);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = product_tail(acc, digits, y, key + (size_t)i * ggsw_words, nb, sh, rt, s);
-    }
-    if (e != hipSuccess) break;
-    if (lwe_out) {
-      hipLaunchKernelGGL(extract, dim3(blocks_for((uint64_t)nb * per_out)), dim3(256), 0, s,
-                         lwe_out + 2 * b0 * per_out, acc, nb, sh);
-      e = hipGetLastError();
-    } else {
-      e = hipMemcpyAsync(acc_glwe + 2 * b0 * per, acc, (size_t)nb * per * 2 * sizeof(u64), hipMemcpyDeviceToDevice, s);
-    }
-  }
+  // one lane (run_blind_rotation never forks): every L.off is 0 and L.st is s, so the chunk's buffers are the lane's
+  auto init = [&](const Lane& L) -> hipError_t {
+    const u64 *in = lwe_in + L.b0 * (n_lwe + 1), *src = lut ? lut : acc_glwe + 2 * L.b0 * per;
+    const hipError_t e =
+        centered ? launch_body_correction(corr, in, (uint32_t)n_lwe, p.logn + 1, L.nb, L.st) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(init_acc, dim3(blocks_for((uint64_t)L.nb * per)), dim3(256), 0, L.st, acc, src,
+                       (uint64_t)(lut ? 0 : per), in, centered ? corr : (const u64*)nullptr, (uint32_t)n_lwe, pre, L.nb,
+                       sh);
+    return hipGetLastError();
+  };
+  auto step = [&](const Lane& L, uint32_t i) -> hipError_t {
+    hipLaunchKernelGGL(rotate_decompose, dim3(blocks_for((uint64_t)L.nb * per)), dim3(256), 0, L.st, digits, acc,
+                       lwe_in + L.b0 * (n_lwe + 1), (uint32_t)n_lwe, i, pre, L.nb, sh);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : product_tail(acc, digits, y, key + (size_t)i * ggsw_words, L.nb, sh, rt, L.st);
+  };
+  auto finish = [&](const Lane& L) -> hipError_t {
+    if (!lwe_out)
+      return hipMemcpyAsync(acc_glwe + 2 * L.b0 * per, acc, (size_t)L.nb * per * 2 * sizeof(u64),
+                            hipMemcpyDeviceToDevice, L.st);
+    hipLaunchKernelGGL(extract, dim3(blocks_for((uint64_t)L.nb * per_out)), dim3(256), 0, L.st,
+                       lwe_out + 2 * L.b0 * per_out, acc, L.nb, sh);
+    return hipGetLastError();
+  };
+  e = run_blind_rotation(batch, chunk, (uint32_t)n_lwe, 1, s, init, step, finish);
   const hipError_t ef = mi::scratch_free(scratch, s);
   return e != hipSuccess ? e : ef;
 }

@@ -25,7 +25,7 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
+#include <type_traits>
 
 #include "scratch.hpp"
 #include "mi_arith.hpp"
@@ -33,6 +33,7 @@
 #include "ntt64_tile.hpp"
 #include "ntt64_tile_asm.hpp"
 #include "pbs_device.hpp"
+#include "pbs_passes.hpp"
 
 namespace mi {
 namespace pbs {
@@ -41,9 +42,6 @@ struct LargeShape {
   uint32_t logn, n, k, level;
   int base_log;
 };
-
-__device__ __forceinline__ uint64_t grid_stride_start() { return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ uint64_t grid_stride() { return (uint64_t)gridDim.x * blockDim.x; }
 
 // signed decomposition of one GLWE coefficient into `level` digits mod p, least significant level first (the
 // order the reference's iterator yields them and the GGSW stores its blocks): BNF = decomposer.rs:156-185 +
@@ -304,6 +302,13 @@ __global__ __launch_bounds__(256) void large_rotdec_tile(u64* __restrict__ digit
   }
 }
 
+// f(std::bool_constant<flag>): a run-time flag (the NTT variant, CMUX, the only-pass top, ...) as a kernel's template
+// argument
+template <class F>
+static auto with_flag(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
 template <int K, bool BNF>
 static hipError_t rotdec_top_launch(bool only, u64* digits, const u64* acc, const u64* lwe_in, uint32_t n_lwe,
                                     uint32_t step, uint32_t nb, const LargeShape& sh, const u64* tw, const u64* twist,
@@ -311,22 +316,18 @@ static hipError_t rotdec_top_launch(bool only, u64* digits, const u64* acc, cons
   if constexpr (K >= 4) {
     if ((sh.n >> K) >= 64) {  // the cooperative tile (>= one 64-column tile)
       const dim3 tgrid((unsigned)(((uint64_t)sh.n >> K) / 64), nb * (sh.k + 1));
-      if (only)
-        hipLaunchKernelGGL((large_rotdec_tile<K, BNF, true>), tgrid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step,
-                           sh, twist);
-      else
-        hipLaunchKernelGGL((large_rotdec_tile<K, BNF, false>), tgrid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step,
-                           sh, twist);
+      with_flag(only, [&](auto O) {
+        hipLaunchKernelGGL((large_rotdec_tile<K, BNF, O>), tgrid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step, sh,
+                           twist);
+      });
       return hipGetLastError();
     }
   }
   const dim3 grid((unsigned)((((uint64_t)sh.n >> K) + 255) / 256), nb * (sh.k + 1));
-  if (only)
-    hipLaunchKernelGGL((large_rotdec_top<K, BNF, true>), grid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step, sh,
-                       tw, twist);
-  else
-    hipLaunchKernelGGL((large_rotdec_top<K, BNF, false>), grid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step, sh,
-                       tw, twist);
+  with_flag(only, [&](auto O) {
+    hipLaunchKernelGGL((large_rotdec_top<K, BNF, O>), grid, dim3(256), 0, s, digits, acc, lwe_in, n_lwe, step, sh, tw,
+                       twist);
+  });
   return hipGetLastError();
 }
 
@@ -507,15 +508,6 @@ __global__ __launch_bounds__(256) void large_accumulate(u64* __restrict__ acc, c
   }
 }
 
-// centered_binary_ms_body_correction_to_add (algorithms/modulus_switch.rs:60-104), one workgroup per ciphertext
-__global__ __launch_bounds__(256) void large_body_correction(u64* __restrict__ corr, const u64* __restrict__ lwe_in,
-                                                             uint32_t n_lwe, unsigned log_mod) {
-  __shared__ u64 sh[512];
-  const u64 v = centered_body_correction<256>(lwe_in + (uint64_t)blockIdx.x * (n_lwe + 1), n_lwe, log_mod,
-                                              (int)threadIdx.x, sh);
-  if (threadIdx.x == 0) corr[blockIdx.x] = v;
-}
-
 // BNF: rotate by -ms(body [+ centered correction]) (ntt64_bnf_pbs.rs:262-270); Solinas: the LUT was pre-rotated;
 // then sample extraction of coefficient 0 (glwe_sample_extraction.rs:89-160): out[c N] = A_c[0],
 // out[c N + j] = -A_c[N - j], out[k N] = B[0]
@@ -565,11 +557,6 @@ __global__ __launch_bounds__(256) void large_modswitch_to_prime(u64* __restrict_
   }
 }
 
-inline unsigned blocks_for(uint64_t total) {
-  const uint64_t b = (total + 255) / 256;
-  return (unsigned)std::min<uint64_t>(b, 65536);
-}
-
 // the plan's transform: the split engine (launch_ntt_split) when the plan has one, else the register-window passes
 inline hipError_t ntt_large(bool fwd, int logn, u64* d, size_t batch, size_t stride, const u64* tw,
                             const SplitTw* split, hipStream_t s) {
@@ -577,22 +564,14 @@ inline hipError_t ntt_large(bool fwd, int logn, u64* d, size_t batch, size_t str
   return launch_ntt(fwd, logn, true, MontParams{}, d, batch, stride, tw, s);
 }
 
-// ciphertexts per chunk: the digits, products and accumulators of one chunk stay below ~4 GiB of scratch (of 288 GB)
-inline size_t chunk_for(const LargeShape& sh, size_t batch) {
-  const size_t per_item = ((size_t)sh.level + 2) * (sh.k + 1) * sh.n * sizeof(u64);
-  return std::max<size_t>(1, std::min(batch, ((size_t)4 << 30) / per_item));
-}
+// scratch of one chunk item: its digits (level GLWEs), products and accumulator (the chunk size of chunk_items)
+inline size_t item_bytes(const LargeShape& sh) { return ((size_t)sh.level + 2) * (sh.k + 1) * sh.n * sizeof(u64); }
 
 }  // namespace pbs
 
-// Lanes: a chunk of >= PBS_LANE_MIN ciphertexts is split into mi::pbs_lane_count() parts (default 2, >= 16 ciphertexts
-// each), the first on the caller's stream and the others on pooled side streams (mi::StreamFork), their launches
-// interleaved step by step.  Each ciphertext's blind rotation is independent, so the parts share nothing but the key,
-// and the GPU overlaps one part's memory-bound launches (the rotation + decomposition pass, the MAC, the accumulating
-// inverse pass) with another's issue-bound transform bodies.
-static constexpr uint32_t PBS_LANE_MIN = 64;
-
-
+// The chunk loop and the lanes are run_blind_rotation's (pbs_passes.hpp), two lanes by default: one lane's memory-bound
+// launches (the rotation + decomposition pass, the MAC, the accumulating inverse pass) overlap the other's issue-bound
+// transform bodies.  Here: a chunk's scratch layout and what a lane launches at init, at a CMUX step and at the end.
 hipError_t launch_pbs_large(int logn, int k, bool bnf, int level, uint64_t* out, const uint64_t* lwe_in,
                             const PbsIo& io, const uint64_t* bsk, size_t n_lwe, size_t batch, int base_log,
                             const uint64_t* tw, const uint64_t* itw, int centered, hipStream_t s,
@@ -600,124 +579,92 @@ hipError_t launch_pbs_large(int logn, int k, bool bnf, int level, uint64_t* out,
   using namespace pbs;
   if (batch == 0) return hipSuccess;
   const LargeShape sh{(uint32_t)logn, 1u << logn, (uint32_t)k, (uint32_t)level, base_log};
-  const size_t per = (size_t)(k + 1) * sh.n, chunk = chunk_for(sh, batch);
+  const size_t per = (size_t)(k + 1) * sh.n, chunk = chunk_items(item_bytes(sh), batch);
   const size_t ggsw_len = (size_t)level * (k + 1) * per;
   u64 *scratch = nullptr;
   hipError_t e = mi::scratch_alloc((void**)&scratch, (chunk * ((size_t)level + 2) * per + chunk) * sizeof(u64), s);
   if (e != hipSuccess) return e;
+  // a lane's inputs and its slices of the chunk's digits, products, accumulators and body corrections (from its L.off)
+  struct Part {
+    const u64* in;
+    u64 *digits, *y, *acc, *corr;
+  };
+  auto part = [&](const Lane& L) {
+    const size_t o = L.off;
+    return Part{lwe_in + L.b0 * (n_lwe + 1), scratch + o * level * per, scratch + (chunk * level + o) * per,
+                scratch + (chunk * (level + 1) + o) * per, scratch + chunk * (level + 2) * per + o};
+  };
   int k0 = 0;
   bool only = false;
   if (split) split_first_pass(logn, &k0, &only);
   // r5: the MAC fused into the inverse's bodies (ntt64_tw.hip ntt_tw_inv_mac_kernel) where generated (l (k + 1) in
   // {2, 3, 4, 6, 8}); other shapes run the separate MAC pass
   const bool mac_fused = split && inv_mac_supported(level, k + 1);
-  // one lane's share of a chunk: ciphertexts [b0, b0 + nb) of the batch, its scratch slices, its stream
-  struct Lane {
-    size_t b0;
-    uint32_t nb;
-    hipStream_t st;
-    const u64* in;
-    u64 *digits, *y, *acc, *corr;
-  };
   auto init = [&](const Lane& L) -> hipError_t {
-    const uint64_t elems = (uint64_t)L.nb * per;
-    if (bnf)
-      hipLaunchKernelGGL(large_init_acc<true>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.acc, io,
-                         (uint64_t)L.b0, L.in, (uint32_t)n_lwe, L.nb, sh);
-    else
-      hipLaunchKernelGGL(large_init_acc<false>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.acc, io,
-                         (uint64_t)L.b0, L.in, (uint32_t)n_lwe, L.nb, sh);
+    const Part p = part(L);
+    with_flag(bnf, [&](auto B) {
+      hipLaunchKernelGGL(large_init_acc<B>, dim3(blocks_for((uint64_t)L.nb * per)), dim3(256), 0, L.st, p.acc, io,
+                         (uint64_t)L.b0, p.in, (uint32_t)n_lwe, L.nb, sh);
+    });
     return hipGetLastError();
   };
   auto step = [&](const Lane& L, uint32_t i) -> hipError_t {  // CMUX step i of the lane's blind rotations
+    const Part p = part(L);
     const uint32_t nb = L.nb;
     const uint64_t elems = (uint64_t)nb * per;
     hipError_t e;
     if (split) {  // rotation + decomposition + the transform's first pass in one kernel, then the rest of the transform
-      e = bnf ? rotdec_top<true>(k0, only, L.digits, L.acc, L.in, (uint32_t)n_lwe, i, nb, sh, tw, split->blk_fwd, L.st)
-              : rotdec_top<false>(k0, only, L.digits, L.acc, L.in, (uint32_t)n_lwe, i, nb, sh, tw, split->blk_fwd, L.st);
+      e = with_flag(bnf, [&](auto B) {
+        return rotdec_top<B>(k0, only, p.digits, p.acc, p.in, (uint32_t)n_lwe, i, nb, sh, tw, split->blk_fwd, L.st);
+      });
       if (e == hipSuccess)
-        e = launch_ntt_split(true, logn, L.digits, (size_t)nb * level * (k + 1), sh.n, tw, *split, L.st, nullptr, 0,
+        e = launch_ntt_split(true, logn, p.digits, (size_t)nb * level * (k + 1), sh.n, tw, *split, L.st, nullptr, 0,
                              true);
     } else {
-      if (bnf)
-        hipLaunchKernelGGL(large_rotate_decompose<true>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.digits, L.acc,
-                           L.in, (uint32_t)n_lwe, i, nb, sh);
-      else
-        hipLaunchKernelGGL(large_rotate_decompose<false>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.digits, L.acc,
-                           L.in, (uint32_t)n_lwe, i, nb, sh);
-      e = ntt_large(true, logn, L.digits, (size_t)nb * level * (k + 1), sh.n, tw, split, L.st);
+      with_flag(bnf, [&](auto B) {
+        hipLaunchKernelGGL(large_rotate_decompose<B>, dim3(blocks_for(elems)), dim3(256), 0, L.st, p.digits, p.acc,
+                           p.in, (uint32_t)n_lwe, i, nb, sh);
+      });
+      e = ntt_large(true, logn, p.digits, (size_t)nb * level * (k + 1), sh.n, tw, split, L.st);
     }
     if (e != hipSuccess) return e;
     if (mac_fused)  // the MAC formed on load by the inverse's 2048-block bodies, then the inverse's top passes
-      return (e = launch_ntt_tw_inv_mac(L.y, L.digits, bsk + (size_t)i * ggsw_len, nb, k + 1, level, logn,
+      return (e = launch_ntt_tw_inv_mac(p.y, p.digits, bsk + (size_t)i * ggsw_len, nb, k + 1, level, logn,
                                          split->body_inv, L.st)) != hipSuccess
                  ? e
-                 : launch_ntt_split(false, logn, L.y, (size_t)nb * (k + 1), sh.n, itw, *split, L.st, L.acc,
+                 : launch_ntt_split(false, logn, p.y, (size_t)nb * (k + 1), sh.n, itw, *split, L.st, p.acc,
                                     bnf ? 1 : 2, true);
-    e = launch_large_mac(L.y, L.digits, bsk + (size_t)i * ggsw_len, nb, sh, (u64)0, nullptr, 1u, L.st);
+    e = launch_large_mac(p.y, p.digits, bsk + (size_t)i * ggsw_len, nb, sh, (u64)0, nullptr, 1u, L.st);
     if (e != hipSuccess) return e;
     if (split)  // the inverse's last pass accumulates into acc itself (launch_ntt_split acc_mode)
-      return launch_ntt_split(false, logn, L.y, (size_t)nb * (k + 1), sh.n, itw, *split, L.st, L.acc, bnf ? 1 : 2);
-    e = ntt_large(false, logn, L.y, (size_t)nb * (k + 1), sh.n, itw, split, L.st);
+      return launch_ntt_split(false, logn, p.y, (size_t)nb * (k + 1), sh.n, itw, *split, L.st, p.acc, bnf ? 1 : 2);
+    e = ntt_large(false, logn, p.y, (size_t)nb * (k + 1), sh.n, itw, split, L.st);
     if (e != hipSuccess) return e;
-    if (bnf)
-      hipLaunchKernelGGL(large_accumulate<true>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.acc, L.y, nb, sh,
+    with_flag(bnf, [&](auto B) {
+      hipLaunchKernelGGL(large_accumulate<B>, dim3(blocks_for(elems)), dim3(256), 0, L.st, p.acc, p.y, nb, sh,
                          (const uint32_t*)nullptr, 1u);
-    else
-      hipLaunchKernelGGL(large_accumulate<false>, dim3(blocks_for(elems)), dim3(256), 0, L.st, L.acc, L.y, nb, sh,
-                         (const uint32_t*)nullptr, 1u);
+    });
     return hipGetLastError();
   };
-  auto finish = [&](const Lane& L) -> hipError_t {  // body correction, final rotation + extraction
-    const uint32_t nb = L.nb;
+  // body correction, final rotation + extraction; outputs are indexed by the lane's global b0
+  auto finish = [&](const Lane& L) -> hipError_t {
+    const Part p = part(L);
     const bool corr_on = bnf && centered;
-    if (corr_on)
-      hipLaunchKernelGGL(large_body_correction, dim3(nb), dim3(256), 0, L.st, L.corr, L.in, (uint32_t)n_lwe,
-                         (unsigned)(logn + 1));
-    const u64* cr = corr_on ? L.corr : (const u64*)nullptr;
-    if (io.glwe_out) {
-      const uint64_t outs = (uint64_t)nb * per;
-      u64* o = io.glwe_out + L.b0 * per;
-      if (bnf)
-        hipLaunchKernelGGL((large_extract<true, true>), dim3(blocks_for(outs)), dim3(256), 0, L.st, o, L.acc, L.in, cr,
-                           (uint32_t)n_lwe, nb, sh, io, (uint64_t)L.b0);
-      else
-        hipLaunchKernelGGL((large_extract<false, true>), dim3(blocks_for(outs)), dim3(256), 0, L.st, o, L.acc, L.in,
-                           cr, (uint32_t)n_lwe, nb, sh, io, (uint64_t)L.b0);
-    } else {
-      const uint64_t outs = (uint64_t)nb * ((uint64_t)k * sh.n + 1);
-      u64* o = out + L.b0 * ((size_t)k * sh.n + 1);
-      if (bnf)
-        hipLaunchKernelGGL((large_extract<true, false>), dim3(blocks_for(outs)), dim3(256), 0, L.st, o, L.acc, L.in,
-                           cr, (uint32_t)n_lwe, nb, sh, io, (uint64_t)L.b0);
-      else
-        hipLaunchKernelGGL((large_extract<false, false>), dim3(blocks_for(outs)), dim3(256), 0, L.st, o, L.acc, L.in,
-                           cr, (uint32_t)n_lwe, nb, sh, io, (uint64_t)L.b0);
-    }
+    const hipError_t e =
+        corr_on ? launch_body_correction(p.corr, p.in, (uint32_t)n_lwe, logn + 1, L.nb, L.st) : hipSuccess;
+    if (e != hipSuccess) return e;
+    const u64* cr = corr_on ? p.corr : (const u64*)nullptr;
+    const size_t per_out = io.glwe_out ? per : (size_t)k * sh.n + 1;
+    u64* o = (io.glwe_out ? io.glwe_out : out) + L.b0 * per_out;
+    with_flag(bnf, [&](auto B) {
+      with_flag(io.glwe_out != nullptr, [&](auto G) {
+        hipLaunchKernelGGL((large_extract<B, G>), dim3(blocks_for((uint64_t)L.nb * per_out)), dim3(256), 0, L.st, o,
+                           p.acc, p.in, cr, (uint32_t)n_lwe, L.nb, sh, io, (uint64_t)L.b0);
+      });
+    });
     return hipGetLastError();
   };
-  for (size_t c0 = 0; c0 < batch && e == hipSuccess; c0 += chunk) {
-    const uint32_t nb = (uint32_t)std::min(chunk, batch - c0);
-    mi::StreamFork fork;
-    const int want = nb >= PBS_LANE_MIN ? std::min<int>(mi::pbs_lane_count(2), (int)(nb / 16)) : 1;
-    if (want > 1) (void)fork.fork(s, want - 1);  // fewer lanes when a side stream cannot be had
-    const int lanes = 1 + fork.sides();
-    Lane L[1 + mi::StreamFork::MAX_SIDE];
-    for (int j = 0, off = 0; j < lanes; ++j) {
-      const uint32_t n = nb / lanes + ((uint32_t)j < nb % lanes ? 1u : 0u);
-      L[j] = Lane{c0 + off, n, j == 0 ? s : fork.side(j - 1), lwe_in + (c0 + off) * (n_lwe + 1),
-                  scratch + (size_t)off * level * per, scratch + chunk * level * per + (size_t)off * per,
-                  scratch + chunk * (level + 1) * per + (size_t)off * per, scratch + chunk * (level + 2) * per + off};
-      off += (int)n;
-    }
-    for (int j = 0; j < lanes && e == hipSuccess; ++j) e = init(L[j]);
-    for (uint32_t i = 0; i < n_lwe && e == hipSuccess; ++i)
-      for (int j = 0; j < lanes && e == hipSuccess; ++j) e = step(L[j], i);
-    for (int j = 0; j < lanes && e == hipSuccess; ++j) e = finish(L[j]);
-    const hipError_t ej = fork.join();  // the caller's stream after the side lane (also on error: scratch ordering)
-    if (e == hipSuccess) e = ej;
-  }
+  e = run_blind_rotation(batch, chunk, (uint32_t)n_lwe, 2, s, init, step, finish);
   const hipError_t ef = mi::scratch_free(scratch, s);
   return e != hipSuccess ? e : ef;
 }
@@ -744,7 +691,7 @@ hipError_t launch_ext_product_large(int logn, int k, bool bnf, bool cmux, int le
   using namespace pbs;
   if (batch == 0) return hipSuccess;
   const LargeShape sh{(uint32_t)logn, 1u << logn, (uint32_t)k, (uint32_t)level, base_log};
-  const size_t per = (size_t)(k + 1) * sh.n, chunk = chunk_for(sh, batch);
+  const size_t per = (size_t)(k + 1) * sh.n, chunk = chunk_items(item_bytes(sh), batch);
   u64* scratch = nullptr;
   hipError_t e = mi::scratch_alloc((void**)&scratch, chunk * ((size_t)level + 1) * per * sizeof(u64), s);
   if (e != hipSuccess) return e;
@@ -756,15 +703,12 @@ hipError_t launch_ext_product_large(int logn, int k, bool bnf, bool cmux, int le
     u64* o = out + b0 * per;
     u64* g = glwe + b0 * per;
     const uint32_t* gi = gidx ? gidx + b0 : nullptr;
-#define MI_LARGE_DEC(B, C)                                                                                          \
-  hipLaunchKernelGGL((large_glwe_decompose<B, C>), dim3(blocks_for(elems)), dim3(256), 0, s, digits, g, o, nb, sh, gi, \
-                     n_ggsw)
-    if (bnf) {
-      if (cmux) MI_LARGE_DEC(true, true); else MI_LARGE_DEC(true, false);
-    } else {
-      if (cmux) MI_LARGE_DEC(false, true); else MI_LARGE_DEC(false, false);
-    }
-#undef MI_LARGE_DEC
+    with_flag(bnf, [&](auto B) {
+      with_flag(cmux, [&](auto C) {
+        hipLaunchKernelGGL((large_glwe_decompose<B, C>), dim3(blocks_for(elems)), dim3(256), 0, s, digits, g, o, nb, sh,
+                           gi, n_ggsw);
+      });
+    });
     e = ntt_large(true, logn, digits, (size_t)nb * level * (k + 1), sh.n, tw, split, s);
     if (e != hipSuccess) break;
     // BNF GGSWs are the reference's Raw NTT keys: the product is normalised here (ntt64_bnf_pbs.rs:670)
@@ -772,10 +716,9 @@ hipError_t launch_ext_product_large(int logn, int k, bool bnf, bool cmux, int le
     if (e != hipSuccess) break;
     e = ntt_large(false, logn, y, (size_t)nb * (k + 1), sh.n, itw, split, s);
     if (e != hipSuccess) break;
-    if (bnf)
-      hipLaunchKernelGGL(large_accumulate<true>, dim3(blocks_for(elems)), dim3(256), 0, s, o, y, nb, sh, gi, n_ggsw);
-    else
-      hipLaunchKernelGGL(large_accumulate<false>, dim3(blocks_for(elems)), dim3(256), 0, s, o, y, nb, sh, gi, n_ggsw);
+    with_flag(bnf, [&](auto B) {
+      hipLaunchKernelGGL(large_accumulate<B>, dim3(blocks_for(elems)), dim3(256), 0, s, o, y, nb, sh, gi, n_ggsw);
+    });
     e = hipGetLastError();
   }
   const hipError_t ef = mi::scratch_free(scratch, s);

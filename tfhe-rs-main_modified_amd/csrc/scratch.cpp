@@ -280,8 +280,6 @@ hipError_t StreamFork::join() {
   return first;
 }
 
-int pbs_lane_count(int dflt) { return std::max(1, std::min(dflt, 1 + StreamFork::MAX_SIDE)); }
-
 size_t scratch_bytes(int device) {
   Pool& P = pool();
   std::lock_guard<std::mutex> lk(P.mu);

@@ -49,9 +49,11 @@ class ScratchBuf {
 };
 
 // Pooled non-blocking side streams of the current device, for an entry point that splits its batch over the caller's
-// stream and up to MAX_SIDE more (pbs_large.hip, fft64_generic.hip): fork() orders each side stream after the work
-// already queued on the caller's stream, join() orders the caller's stream after everything queued on the side
-// streams and returns them to the pool.  No host synchronisation either way (events only).
+// stream and up to MAX_SIDE more: fork() orders each side stream after the work already queued on the caller's stream,
+// join() orders the caller's stream after everything queued on the side streams and returns them to the pool.  No host
+// synchronisation either way (events only).  Its one user is run_blind_rotation (pbs_passes.hpp), which owns the chunks
+// and lanes of the multi-pass blind rotations: chunk_items, lanes_wanted and lane_part there say how a batch is cut; the
+// engines (pbs_large.hip, fft64_generic.hip, pbs128.hip) keep their scratch layout and their default lane count.
 class StreamFork {
  public:
   static constexpr int MAX_SIDE = 3;
@@ -69,9 +71,5 @@ class StreamFork {
   hipStream_t caller_ = nullptr, side_[MAX_SIDE] = {};
   int device_ = 0, n_ = 0;
 };
-
-// lanes a batched blind rotation splits a chunk into: the caller's measured default for its shape, clamped to
-// 1 ... 1 + MAX_SIDE (r6: no environment override; the lane sweeps of r4-r5 are in DESIGN.md section 4)
-int pbs_lane_count(int dflt);
 
 }  // namespace mi

@@ -113,12 +113,16 @@ __device__ u64 centered_body_correction(const u64* __restrict__ lwe, uint32_t n_
   sh[gt] = sum_half;
   sh[TG + gt] = (u64)sum_hed;
   __syncthreads();
-  for (int s = TG / 2; s > 0; s >>= 1) {
-    if (gt < s) {
+  // TG = 64 (k + 1) is no power of two at k = 2 (192 -> ... -> 3 -> 2 -> 1): the upper part of the `live` entries
+  // folds onto the lower one, and an odd count keeps its middle entry for the next round
+  for (int live = TG; live > 1;) {
+    const int s = (live + 1) / 2;
+    if (gt + s < live) {
       sh[gt] += sh[gt + s];
       sh[TG + gt] = (u64)((int64_t)sh[TG + gt] + (int64_t)sh[TG + gt + s]);
     }
     __syncthreads();
+    live = s;
   }
   const u64 total_half = sh[0];
   const int64_t total_hed = (int64_t)sh[TG];

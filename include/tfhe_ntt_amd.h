@@ -592,6 +592,55 @@ int mi_lwe_modulus_switch32_batch(uint64_t *switched, const uint32_t *lwe_in, si
 int mi_lwe_modulus_switch_batch(uint64_t *switched, const uint64_t *lwe_in, size_t lwe_dim, size_t batch,
                                 int log_modulus, int ms_mode, int device, void *stream);
 
+/* ---- Modulus switch noise reduction: the drift technique ------------------------------------------------------
+ * ModulusSwitchConfiguration::DriftTechniqueNoiseReduction (shortint/server_key/modulus_switch_noise_reduction.rs:
+ * 325-383), what every classic *_KS_PBS_TUNIFORM_2M128 parameter set runs between its keyswitch and its bootstrap
+ * (shortint/parameters/v1_1/classic/tuniform/p_fail_2_minus_128/ks_pbs.rs:29-122; https://eprint.iacr.org/2024/1718):
+ * core_crypto/algorithms/modulus_switch_noise_reduction.rs.  An input LWE whose modulus switch noise measure exceeds
+ * ms_bound gets the first of the key's encryptions of zero added that brings the measure under the bound, or, when
+ * none does, the first one with the smallest measure (the unmodified input wins ties).  The measure's two f64 sums
+ * run over the mask in the reference's order with a separate multiply and add, so the measures, the chosen
+ * candidates and the outputs are the reference's bit for bit.  Native u64 modulus only, as the reference asserts
+ * (:131-136).
+ * mi_ms_noise_key_create takes the ModulusSwitchNoiseReductionKey's modulus_switch_zeros in the LweCiphertextList
+ * layout as a device pointer, zeros_count rows of lwe_dim + 1 u64, and prepares a private device copy on `stream`
+ * (the stream that produced `zeros`), which it synchronises; the caller's buffer may be freed afterwards.  The
+ * modular variance of the measure is ms_input_variance * 2^64 * 2^64 (dispersion.rs:258-262).  Checked before any
+ * device call, the first failing rule answering, all MI_ERR_INVALID_ARG: "zeros is NULL"; "out_key is NULL";
+ * lwe_dim outside [1, 2^24): "lwe dimension out of range"; zeros_count == 0: "expected at least one encryption of
+ * zero" (the reference's assert, :126-130); zeros_count >= 2^32: "zeros_count out of range"; a NaN among the three
+ * doubles: "ms_bound, ms_r_sigma_factor and ms_input_variance must not be NaN"; ms_r_sigma_factor < 0 or
+ * ms_input_variance < 0: "ms_r_sigma_factor and ms_input_variance must not be negative".  +inf is a legal bound.
+ * Every batch entry: device pointers, async on `stream`; a NULL key is MI_ERR_INVALID_ARG "key is NULL"; log_modulus
+ * outside [1, 64] is MI_ERR_INVALID_ARG (at 64 the rounding is the identity and every error 0, fft_impl/common.rs:
+ * 10-23); batch = 0 is MI_OK. */
+typedef struct mi_ms_noise_key mi_ms_noise_key;
+int mi_ms_noise_key_create(const uint64_t *zeros, size_t lwe_dim, size_t zeros_count, double ms_bound,
+                           double ms_r_sigma_factor, double ms_input_variance, int device, void *stream,
+                           mi_ms_noise_key **out_key);
+int mi_ms_noise_key_destroy(mi_ms_noise_key *key);
+int mi_ms_noise_key_info(const mi_ms_noise_key *key, size_t *lwe_dim, size_t *zeros_count, double *ms_bound,
+                         double *ms_r_sigma_factor, double *ms_input_variance);
+/* measure_modulus_switch_noise_estimation_for_binary_key (:71-86): measures[b * stride] for lwe_in[b]; with
+ * all_candidates != 0 stride = 1 + zeros_count and measures[b * stride + 1 + c] is the measure of lwe_in[b] + zero[c];
+ * else stride = 1. */
+int mi_lwe_ms_noise_measure_batch(const mi_ms_noise_key *key, double *measures, const uint64_t *lwe_in, size_t batch,
+                                  int log_modulus, int all_candidates, void *stream);
+/* choose_candidate_to_improve_modulus_switch_noise_for_binary_key (:99-195): candidate[b] = -1 (NoAddition) or the
+ * index; satisfied[b] = 1 (SatisfyingBound) or 0 (BestNotSatisfyingBound). */
+int mi_lwe_ms_noise_choose_batch(const mi_ms_noise_key *key, int64_t *candidate, int32_t *satisfied,
+                                 const uint64_t *lwe_in, size_t batch, int log_modulus, void *stream);
+/* improve_lwe_ciphertext_modulus_switch_noise_for_binary_key (:202-242); lwe_out may be lwe_in (the reference's
+ * in-place form); candidate / satisfied may be NULL. */
+int mi_lwe_ms_noise_improve_batch(const mi_ms_noise_key *key, uint64_t *lwe_out, const uint64_t *lwe_in, size_t batch,
+                                  int log_modulus, int64_t *candidate, int32_t *satisfied, void *stream);
+/* ModulusSwitchNoiseReductionKey::improve_noise_and_modulus_switch (shortint/server_key/
+ * modulus_switch_noise_reduction.rs:102-118), materialised: the improved LWE through the standard switch of
+ * mi_lwe_modulus_switch_batch, values in [0, 2^log_modulus), the MI_MS_PRE_SWITCHED input of every blind rotation /
+ * PBS entry. */
+int mi_lwe_ms_noise_improve_and_switch_batch(const mi_ms_noise_key *key, uint64_t *switched, const uint64_t *lwe_in,
+                                             size_t batch, int log_modulus, void *stream);
+
 /* ---- LWE packing keyswitch and GLWE compression ---------------------------------------------------------------
  * What shortint's CompressedCiphertextList is built on (COMP_PARAM_MESSAGE_2_CARRY_2: 2048 -> k = 4, N = 256,
  * base 2^4, 3 levels, 256 LWEs per GLWE, storage log modulus 12; shortint/parameters/v1_4/list_compression/).

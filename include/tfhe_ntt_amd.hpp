@@ -351,6 +351,38 @@ inline void lwe_ciphertext_modulus_switch(const uint64_t* lwe_in, uint64_t* swit
                                     centered ? MI_MS_CENTERED : MI_MS_STANDARD, device, stream));
 }
 
+// ModulusSwitchNoiseReductionKey (shortint/server_key/modulus_switch_noise_reduction.rs:35-119) over
+// core_crypto/algorithms/modulus_switch_noise_reduction.rs, batched; move-only
+class ModulusSwitchNoiseReductionKey {
+ public:
+  // modulus_switch_zeros: zeros_count device rows of lwe_dimension + 1 u64 (the LweCiphertextList layout)
+  ModulusSwitchNoiseReductionKey(const uint64_t* modulus_switch_zeros, size_t lwe_dimension, size_t zeros_count,
+                                 double ms_bound, double ms_r_sigma_factor, double ms_input_variance, int device = 0,
+                                 void* stream = nullptr) {
+    check(mi_ms_noise_key_create(modulus_switch_zeros, lwe_dimension, zeros_count, ms_bound, ms_r_sigma_factor,
+                                 ms_input_variance, device, stream, &raw_));
+  }
+  ModulusSwitchNoiseReductionKey(ModulusSwitchNoiseReductionKey&& o) noexcept : raw_(std::exchange(o.raw_, nullptr)) {}
+  ModulusSwitchNoiseReductionKey(const ModulusSwitchNoiseReductionKey&) = delete;
+  ModulusSwitchNoiseReductionKey& operator=(const ModulusSwitchNoiseReductionKey&) = delete;
+  ~ModulusSwitchNoiseReductionKey() {
+    if (raw_) (void)mi_ms_noise_key_destroy(raw_);
+  }
+  const mi_ms_noise_key* raw() const noexcept { return raw_; }
+  // improve_modulus_switch_noise (:85-100), in place over a batch
+  void improve_modulus_switch_noise(uint64_t* lwe, size_t batch, int log_modulus, void* stream = nullptr) const {
+    check(mi_lwe_ms_noise_improve_batch(raw_, lwe, lwe, batch, log_modulus, nullptr, nullptr, stream));
+  }
+  // improve_noise_and_modulus_switch (:102-118): switched gets the MI_MS_PRE_SWITCHED values in [0, 2^log_modulus)
+  void improve_noise_and_modulus_switch(const uint64_t* lwe_in, uint64_t* switched, size_t batch, int log_modulus,
+                                        void* stream = nullptr) const {
+    check(mi_lwe_ms_noise_improve_and_switch_batch(raw_, switched, lwe_in, batch, log_modulus, stream));
+  }
+
+ private:
+  mi_ms_noise_key* raw_ = nullptr;
+};
+
 // On-disk NTT bootstrap key (entities/ntt_lwe_bootstrap_key.rs:26-33): plain bincode or the versioned
 // form, parsed and written by the library (mi_ntt_bsk_parse / mi_ntt_bsk_write, pure host code, no
 // device needed); the layouts are documented in include/tfhe_ntt_amd.h.  Same bytes as

@@ -154,6 +154,15 @@ _SIGS = {
     "mi_lwe_keyswitch32_batch": (_int, [_vp, _vp, _vp, _sz, _vp]),
     "mi_lwe_modulus_switch32_batch": (_int, [_vp, _vp, _sz, _sz, _int, _int, _int, _vp]),
     "mi_lwe_modulus_switch_batch": (_int, [_vp, _vp, _sz, _sz, _int, _int, _int, _vp]),
+    "mi_ms_noise_key_create": (_int, [_vp, _sz, _sz, ctypes.c_double, ctypes.c_double, ctypes.c_double, _int, _vp,
+                                      ctypes.POINTER(_vp)]),
+    "mi_ms_noise_key_destroy": (_int, [_vp]),
+    "mi_ms_noise_key_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double),
+                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "mi_lwe_ms_noise_measure_batch": (_int, [_vp, _vp, _vp, _sz, _int, _int, _vp]),
+    "mi_lwe_ms_noise_choose_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _vp]),
+    "mi_lwe_ms_noise_improve_batch": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _vp, _vp]),
+    "mi_lwe_ms_noise_improve_and_switch_batch": (_int, [_vp, _vp, _vp, _sz, _int, _vp]),
     "mi_lwe_pksk_create": (_int, [_vp, _sz, _int, _sz, _int, _int, _int, _vp, ctypes.POINTER(_vp)]),
     "mi_lwe_pksk_destroy": (_int, [_vp]),
     "mi_lwe_pksk_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_sz),

@@ -10,7 +10,8 @@ import re
 import sys
 
 HDR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "tfhe_ntt_amd.h")
-SCALARS = {"size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int",
+SCALARS = {"size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int64_t": "i64", "int32_t": "i32",
+           "int": "c_int",
            "unsigned": "c_uint", "double": "f64", "void": "c_void", "char": "c_char"}
 
 

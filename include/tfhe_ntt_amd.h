@@ -697,9 +697,9 @@ int mi_glwe_extract_batch(uint64_t *glwe, const uint64_t *packed, size_t polynom
  * ggsw.rs:517-567; the exact negacyclic product).  Every u128 crosses this ABI as two little-endian u64 words (lo, hi),
  * as mi_native_polymul_batch takes them; u128 buffers are 16-byte aligned device pointers.
  * Not provided: non-native power-of-two moduli below 2^128 (the closest_representable step of blind_rotate_u128,
- * bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the noise-squashing
- * packing keyswitch (base_log 61 over u128), the C++ mirror, and the serialised Fourier128LweBootstrapKey format (it
- * holds the output of the reference's own FFT and has no meaning here).
+ * bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the C++ mirror,
+ * and the serialised Fourier128LweBootstrapKey format (it holds the output of the reference's own FFT and has no
+ * meaning here).  The packing keyswitch and the compression of its results are the next section.
  *
  * mi_pbs128_limb_plan (no reference counterpart, needs no device): limb_bits = the largest w with
  * R N 2^(base_log - 1) (2^w - 1) <= (p - 1) / 2, R = (k + 1) level, p = 2^64 - 2^32 + 1; n_limbs = ceil(128 / w)
@@ -747,6 +747,61 @@ int mi_blind_rotate128_batch(const mi_pbs128_key *key, uint64_t *acc_glwe, const
  * lwe_out[b] = k polynomial_size + 1 u128. */
 int mi_pbs128_batch(const mi_pbs128_key *key, uint64_t *lwe_out, const uint64_t *lwe_in, const uint64_t *lut,
                     size_t batch, int ms_mode, void *stream);
+
+/* ---- The 128-bit packing keyswitch and compression of noise squashing ---------------------------------------------
+ * What shortint does with the u128 LWEs of the bootstrap above: compress_noise_squashed_ciphertexts_into_list
+ * (shortint/list_compression/noise_squashing_compression.rs:23-118) packs them into GLWEs with
+ * par_keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext at Scalar = u128 and stores them through
+ * CompressedModulusSwitchedGlweCiphertext::compress (CompressedSquashedNoiseCiphertextList).  V1_4_NOISE_SQUASHING_COMP_
+ * PARAM_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M128 (shortint/parameters/v1_4/noise_squashing/p_fail_2_minus_128/mod.rs:
+ * 21-32): base 2^61, 1 level, k = 6, N = 1024, 128 LWEs per GLWE, native u128 modulus, input LWE dimension 4096.
+ * Integer-only and bit-exact; every u128 is two little-endian u64 words (lo, hi), u128 buffers are 16-byte aligned
+ * device pointers, as in the section above.
+ * Not provided: sample extraction of u128 LWEs at a monomial degree (the list's unpack, a client-side step), the
+ * multi-bit 128-bit bootstrap, non-native u128 moduli, the C++ mirror, serialised formats, and a digit pass fused into
+ * the GEMM.
+ *
+ * mi_lwe_pksk128_create takes the reference's LwePackingKeyswitchKey<u128> layout as a device pointer: in_dim blocks
+ * of `level` GLWE ciphertexts of (glwe_dim + 1) * polynomial_size u128, levels stored as
+ * generate_lwe_packing_keyswitch_key writes them (lwe_packing_keyswitch_key_generation.rs:129-156), and prepares a
+ * private device copy of the same size (16 signed bytes per word, for the int8 matrix cores); the preparation runs
+ * on `stream` and synchronises it.  The argument rules of mi_lwe_pksk_create, except: MI_ERR_INVALID_ARG where
+ * SignedDecomposer::<u128>::new asserts (decomposer.rs:86-90: base_log * level outside [1, 127]); MI_ERR_UNSUPPORTED
+ * for base_log > 63 (a digit is held in 64 bits), then beyond the 2^17 GEMM-depth bound of mi_lwe_ksk_create,
+ * in_dim * level * ceil((base_log + 1) / 8) < 2^17. */
+typedef struct mi_lwe_pksk128 mi_lwe_pksk128;
+int mi_lwe_pksk128_create(const uint64_t *pksk, size_t in_dim, int glwe_dim, size_t polynomial_size, int base_log,
+                          int level, int device, void *stream, mi_lwe_pksk128 **out_key);
+int mi_lwe_pksk128_destroy(mi_lwe_pksk128 *key);
+int mi_lwe_pksk128_info(const mi_lwe_pksk128 *key, size_t *in_dim, int *glwe_dim, size_t *polynomial_size,
+                        int *base_log, int *level);
+/* keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext (lwe_packing_keyswitch.rs:296-379, calling :102-187) at
+ * Scalar = u128 over a list of lists, as mi_lwe_packing_keyswitch_batch: n_lwe ciphertexts of in_dim + 1 u128,
+ * ceil(n_lwe / lwe_per_glwe) GLWEs of (glwe_dim + 1) * polynomial_size u128 out, the last one holding the remainder;
+ * lwe_per_glwe = 1 is the single keyswitch over a batch; lwe_per_glwe of 0 or above polynomial_size is
+ * MI_ERR_INVALID_ARG; n_lwe = 0 is MI_OK.  Async on `stream`; stream-ordered scratch of at most 64 MiB of keyswitched
+ * rows (or one row, if larger) plus their digits, freed before return: larger calls run in chunks. */
+int mi_lwe_packing_keyswitch128_batch(const mi_lwe_pksk128 *key, uint64_t *glwe_out, const uint64_t *lwe_in,
+                                      size_t n_lwe, size_t lwe_per_glwe, void *stream);
+/* The u128 words (two u64 each) of one CompressedModulusSwitchedGlweCiphertext<u128>'s PackedIntegers:
+ * ceil((glwe_dim * polynomial_size + bodies_count) * log_modulus / 128)
+ * (compressed_modulus_switched_glwe_ciphertext.rs:229-232).  PackedIntegers<u128> packs into 128-bit words
+ * (packed_integers.rs:39-130); as (lo, hi) u64 pairs that is the same bit string the u64 packer writes, rounded up to
+ * an even u64 word count.  bodies_count <= polynomial_size and 1 <= log_modulus <= 128, as compress asserts
+ * (:191-203); else MI_ERR_INVALID_ARG, here and below. */
+int mi_glwe_compressed_words128(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus,
+                                size_t *words);
+/* CompressedModulusSwitchedGlweCiphertext::compress (:169-220) at Scalar = u128 over a batch: the first
+ * glwe_dim * polynomial_size + bodies_count words of glwe[b] through modulus_switch (fft_impl/common.rs:10-23; the
+ * identity at the production log_modulus 128, where the packing is a copy of those words), packed log_modulus bits
+ * each, little end first, into packed[b] (mi_glwe_compressed_words128 u128).  Device pointers, async on `stream`. */
+int mi_glwe_compress128_batch(uint64_t *packed, const uint64_t *glwe, size_t polynomial_size, int glwe_dim,
+                              size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
+/* CompressedModulusSwitchedGlweCiphertext::extract (:226-256) at Scalar = u128: glwe[b] ((glwe_dim + 1) *
+ * polynomial_size u128) = the unpacked values (packed_integers.rs:132-222) shifted left by 128 - log_modulus, then
+ * polynomial_size - bodies_count zeros. */
+int mi_glwe_extract128_batch(uint64_t *glwe, const uint64_t *packed, size_t polynomial_size, int glwe_dim,
+                             size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
 
 #ifdef __cplusplus
 }

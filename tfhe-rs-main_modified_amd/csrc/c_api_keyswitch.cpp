@@ -1,6 +1,7 @@
 // c_api_keyswitch.cpp — the keyswitch family of the C ABI: the three prepared keys (mi_lwe_ksk, mi_lwe_ksk32,
 // mi_lwe_pksk) over one shared core, the two LWE modulus switches, the packing keyswitch and the GLWE compression
-// (kernels: keyswitch.hip, packing_keyswitch.hip).
+// (kernels: keyswitch.hip, packing_keyswitch.hip), and their u128 twins of the noise-squashing compression
+// (mi_lwe_pksk128, packing_keyswitch128.hip).
 #include <new>
 #include <string>
 
@@ -37,6 +38,14 @@ struct mi_lwe_pksk {
   size_t polynomial_size = 0;
 };
 
+struct mi_lwe_pksk128 {
+  int device = 0;
+  mi::Pks128Geometry geo;
+  void* frag = nullptr;  // 16 signed-byte planes per key word (packing_keyswitch128.hip)
+  int glwe_dim = 0;
+  size_t polynomial_size = 0;
+};
+
 namespace {
 
 // The range rules of the three creates, in their common order.  `own` is the message of the caller's own failed rule
@@ -45,10 +54,12 @@ namespace {
 int check_ks_range(size_t in_dim, const char* own, int base_log, int level, int top) {
   if (in_dim == 0 || in_dim > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "lwe dimension out of range");
   if (own) return fail(MI_ERR_INVALID_ARG, own);
-  // SignedDecomposer::new (decomposer.rs): base_log * level < 64, both >= 1; KS32 (lwe_keyswitch.rs:378-384):
-  // base_log * level <= OutputScalar::BITS
-  if (base_log < 1 || level < 1 || base_log * level > top)
+  // SignedDecomposer::new (decomposer.rs): base_log * level < Scalar::BITS, both >= 1; KS32 (lwe_keyswitch.rs:
+  // 378-384): base_log * level <= OutputScalar::BITS
+  if (base_log < 1 || level < 1 || level > top || base_log * level > top)
     return fail(MI_ERR_INVALID_ARG, "decomposition base_log * level must be in [1, " + std::to_string(top) + "]");
+  // u128 keys only (top = 127): a digit is held in an int64 and split into at most 8 signed bytes
+  if (base_log > 63) return fail(MI_ERR_UNSUPPORTED, "base_log above 63 is not supported (a digit must fit 64 bits)");
   // exact int32 accumulation on the int8 matrix cores: GEMM depth in_dim * level * bytes-per-digit < 2^17
   if ((double)in_dim * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
     return fail(MI_ERR_UNSUPPORTED, "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
@@ -133,12 +144,13 @@ int check_lwe_ms(const void* switched, const void* lwe_in, size_t lwe_dim, size_
 
 // compress's asserts (compressed_modulus_switched_glwe_ciphertext.rs:191-203) and PackedIntegers::pack's
 // (packed_integers.rs:43-44)
-int check_glwe_compress(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus) {
+int check_glwe_compress(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus, int bits = 64) {
   if (polynomial_size == 0 || glwe_dim < 1 || polynomial_size > 0xFFFFFFull ||
       ((size_t)glwe_dim + 1) * polynomial_size > 0xFFFFFFull)
     return fail(MI_ERR_INVALID_ARG, "glwe size out of range");
   if (bodies_count > polynomial_size) return fail(MI_ERR_INVALID_ARG, "bodies_count must be <= polynomial_size");
-  if (log_modulus < 1 || log_modulus > 64) return fail(MI_ERR_INVALID_ARG, "log_modulus must be in [1, 64]");
+  if (log_modulus < 1 || log_modulus > bits)
+    return fail(MI_ERR_INVALID_ARG, "log_modulus must be in [1, " + std::to_string(bits) + "]");
   return MI_OK;
 }
 
@@ -339,6 +351,137 @@ int mi_glwe_extract_batch(uint64_t* glwe, const uint64_t* packed, size_t polynom
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   const hipError_t e = mi::launch_glwe_extract(glwe, packed, polynomial_size, glwe_dim, bodies_count, log_modulus,
                                                batch, (hipStream_t)stream);
+  return e == hipSuccess ? MI_OK : hip_fail(e, "glwe extraction launch");
+}
+
+// ---- The u128 twins: shortint's compression of noise-squashed ciphertexts (shortint/list_compression/
+// noise_squashing_compression.rs:23-118) over lwe_packing_keyswitch.rs:102-187, 296-379 and
+// compressed_modulus_switched_glwe_ciphertext.rs:169-256 at Scalar = u128 ------------------------------------------
+
+int mi_lwe_pksk128_create(const uint64_t* pksk, size_t in_dim, int glwe_dim, size_t polynomial_size, int base_log,
+                          int level, int device, void* stream, mi_lwe_pksk128** out_key) {
+  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
+  *out_key = nullptr;
+  if (!pksk) return fail(MI_ERR_INVALID_ARG, "pksk is NULL");
+  const size_t n = polynomial_size;
+  const char* own = nullptr;
+  if (n == 0 || (n & (n - 1)) != 0)
+    own = "polynomial size must be a power of two";
+  else if (glwe_dim < 1 || n > 0xFFFFFFull || ((size_t)glwe_dim + 1) * n > 0xFFFFFFull)
+    own = "glwe size out of range";
+  // SignedDecomposer::<u128>::new: base_log * level in [1, 127]; then base_log <= 63 and the 2^17 depth rule, whose
+  // bytes per digit are this GEMM's too
+  const int st = check_ks_range(in_dim, own, base_log, level, 127);
+  if (st != MI_OK) return st;
+  mi_lwe_pksk128* key = new (std::nothrow) mi_lwe_pksk128;
+  if (!key) return fail(MI_ERR_OOM, "host allocation failed");
+  key->device = device;
+  key->geo.in_dim = in_dim;
+  key->geo.out_size = ((size_t)glwe_dim + 1) * n;
+  key->geo.base_log = base_log;
+  key->geo.level = level;
+  key->geo.body_col = (size_t)glwe_dim * n;
+  key->glwe_dim = glwe_dim;
+  key->polynomial_size = n;
+  DeviceGuard g(device);
+  if (!g.ok) {
+    delete key;
+    return fail(MI_ERR_INVALID_ARG, "bad device");
+  }
+  if (hipMalloc(&key->frag, mi::pks128_key_bytes(key->geo)) != hipSuccess) {
+    delete key;
+    return fail(MI_ERR_OOM, "packing keyswitch key allocation failed");
+  }
+  hipError_t e = mi::launch_pksk128_prepare(key->frag, pksk, key->geo, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess) {
+    (void)hipFree(key->frag);
+    delete key;
+    return hip_fail(e, "packing keyswitch key preparation");
+  }
+  *out_key = key;
+  return MI_OK;
+}
+
+int mi_lwe_pksk128_destroy(mi_lwe_pksk128* key) {
+  if (!key) return MI_OK;
+  {
+    DeviceGuard g(key->device);
+    if (key->frag) (void)hipFree(key->frag);
+  }
+  delete key;
+  return MI_OK;
+}
+
+int mi_lwe_pksk128_info(const mi_lwe_pksk128* key, size_t* in_dim, int* glwe_dim, size_t* polynomial_size,
+                        int* base_log, int* level) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (in_dim) *in_dim = key->geo.in_dim;
+  if (glwe_dim) *glwe_dim = key->glwe_dim;
+  if (polynomial_size) *polynomial_size = key->polynomial_size;
+  if (base_log) *base_log = key->geo.base_log;
+  if (level) *level = key->geo.level;
+  return MI_OK;
+}
+
+int mi_lwe_packing_keyswitch128_batch(const mi_lwe_pksk128* key, uint64_t* glwe_out, const uint64_t* lwe_in,
+                                      size_t n_lwe, size_t lwe_per_glwe, void* stream) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  // lwe_packing_keyswitch.rs:358-360: lwe_ciphertext_count <= polynomial_size
+  if (lwe_per_glwe == 0 || lwe_per_glwe > key->polynomial_size)
+    return fail(MI_ERR_INVALID_ARG, "lwe_per_glwe must be in [1, polynomial_size]");
+  if (n_lwe == 0) return MI_OK;
+  if (!glwe_out || !lwe_in) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (n_lwe > 0xFFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
+  const hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(key->device);
+  mi::PksPlan plan = mi::pks_plan_rows(key->geo.out_size, 16, n_lwe, lwe_per_glwe);
+  plan.digit_bytes = mi::pks128_digit_bytes(key->geo, plan.rows);
+  // stream-ordered scratch: the GEMM's rows, its int8 digit fragments, the rotate-and-sum pass's partial sums
+  mi::ScratchBuf t(s), digits(s), partials(s);
+  if (!t.alloc(plan.t_bytes) || !digits.alloc(plan.digit_bytes) ||
+      (plan.partial_bytes != 0 && !partials.alloc(plan.partial_bytes)))
+    return fail(MI_ERR_OOM, "scratch allocation failed");
+  const hipError_t e = mi::launch_packing_keyswitch128(glwe_out, lwe_in, key->frag, t.ptr(), digits.ptr(),
+                                                       partials.ptr(), n_lwe, lwe_per_glwe, key->polynomial_size,
+                                                       key->geo, plan, s);
+  return e == hipSuccess ? MI_OK : hip_fail(e, "packing keyswitch launch");
+}
+
+int mi_glwe_compressed_words128(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus,
+                                size_t* words) {
+  if (!words) return fail(MI_ERR_INVALID_ARG, "words is NULL");
+  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus, 128);
+  if (st != MI_OK) return st;
+  *words = mi::glwe_compressed_words128(polynomial_size, glwe_dim, bodies_count, log_modulus);
+  return MI_OK;
+}
+
+int mi_glwe_compress128_batch(uint64_t* packed, const uint64_t* glwe, size_t polynomial_size, int glwe_dim,
+                              size_t bodies_count, int log_modulus, size_t batch, int device, void* stream) {
+  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus, 128);
+  if (st != MI_OK) return st;
+  if (batch == 0) return MI_OK;
+  if (!packed || !glwe) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (batch > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
+  const hipError_t e = mi::launch_glwe_compress128(packed, glwe, polynomial_size, glwe_dim, bodies_count, log_modulus,
+                                                   batch, (hipStream_t)stream);
+  return e == hipSuccess ? MI_OK : hip_fail(e, "glwe compression launch");
+}
+
+int mi_glwe_extract128_batch(uint64_t* glwe, const uint64_t* packed, size_t polynomial_size, int glwe_dim,
+                             size_t bodies_count, int log_modulus, size_t batch, int device, void* stream) {
+  const int st = check_glwe_compress(polynomial_size, glwe_dim, bodies_count, log_modulus, 128);
+  if (st != MI_OK) return st;
+  if (batch == 0) return MI_OK;
+  if (!packed || !glwe) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (batch > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
+  const hipError_t e = mi::launch_glwe_extract128(glwe, packed, polynomial_size, glwe_dim, bodies_count, log_modulus,
+                                                  batch, (hipStream_t)stream);
   return e == hipSuccess ? MI_OK : hip_fail(e, "glwe extraction launch");
 }
 

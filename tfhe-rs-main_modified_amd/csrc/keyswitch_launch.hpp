@@ -51,6 +51,8 @@ struct PksPlan {
   size_t t_bytes = 0, digit_bytes = 0, partial_bytes = 0;
 };
 PksPlan pks_plan(const KsGeometry& g, size_t n_lwe, size_t lwe_per_glwe);
+// the same plan for rows of out_size words of word_bytes bytes; digit_bytes is left 0 (the caller's GEMM sizes it)
+PksPlan pks_plan_rows(size_t out_size, size_t word_bytes, size_t n_lwe, size_t lwe_per_glwe);
 // glwe_out: ceil(n_lwe / lwe_per_glwe) GLWEs of out_size words; t / digits / partials: scratch of the plan's sizes
 hipError_t launch_packing_keyswitch(uint64_t* glwe_out, const uint64_t* lwe_in, const void* frag, void* t, void* digits,
                                     void* partials, size_t n_lwe, size_t lwe_per_glwe, size_t polynomial_size,
@@ -61,5 +63,27 @@ hipError_t launch_glwe_compress(uint64_t* packed, const uint64_t* glwe, size_t p
                                 size_t bodies_count, int log_modulus, size_t batch, hipStream_t s);
 hipError_t launch_glwe_extract(uint64_t* glwe, const uint64_t* packed, size_t polynomial_size, int glwe_dim,
                                size_t bodies_count, int log_modulus, size_t batch, hipStream_t s);
+
+// packing_keyswitch128.hip — the same two operations at Scalar = u128 (shortint's noise-squashing compression):
+// every u128 is two little-endian u64 words, 16-byte aligned.
+struct Pks128Geometry {
+  size_t in_dim = 0, out_size = 0;  // out_size = (k + 1) N u128 key columns
+  int base_log = 0, level = 0;      // base_log <= 63
+  size_t body_col = 0;              // k N
+};
+size_t pks128_key_bytes(const Pks128Geometry& g);                // the prepared key (16 signed-byte planes)
+size_t pks128_digit_bytes(const Pks128Geometry& g, size_t rows);  // the digit fragments of `rows` input rows
+hipError_t launch_pksk128_prepare(void* frag, const uint64_t* pksk, const Pks128Geometry& g, hipStream_t s);
+// plan: pks_plan_rows(out_size, 16, ...) with digit_bytes = pks128_digit_bytes(g, plan.rows)
+hipError_t launch_packing_keyswitch128(uint64_t* glwe_out, const uint64_t* lwe_in, const void* frag, void* t,
+                                       void* digits, void* partials, size_t n_lwe, size_t lwe_per_glwe,
+                                       size_t polynomial_size, const Pks128Geometry& g, const PksPlan& plan,
+                                       hipStream_t s);
+// u128 words of one compressed GLWE: ceil((k N + bodies) log_modulus / 128)
+size_t glwe_compressed_words128(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus);
+hipError_t launch_glwe_compress128(uint64_t* packed, const uint64_t* glwe, size_t polynomial_size, int glwe_dim,
+                                   size_t bodies_count, int log_modulus, size_t batch, hipStream_t s);
+hipError_t launch_glwe_extract128(uint64_t* glwe, const uint64_t* packed, size_t polynomial_size, int glwe_dim,
+                                  size_t bodies_count, int log_modulus, size_t batch, hipStream_t s);
 
 }  // namespace mi

@@ -11,7 +11,8 @@
 // writes one row T[d] per ciphertext into scratch; the list form multiplies row d by X^d and sums the rows of a GLWE
 // (polynomial_wrapping_monic_monomial_mul_assign + slice_wrapping_add_assign, :369-378):
 //   out[g][p][j] = sum_{d < cnt} +- T[g per + d][p N + ((j - d) mod N)], negated when j < d.
-//   * pks_rotate_sum_kernel: one thread per output word (p, j), looping over a slice of d.  For fixed d consecutive j
+//   * pks_rotate_sum_kernel (pks_rotate.hpp, shared with packing_keyswitch128.hip): one thread per output word
+//     (p, j), looping over a slice of d.  For fixed d consecutive j
 //     read consecutive words (a rotation only moves where the 8 N-byte row wraps), so every wave load is one or two
 //     contiguous runs and needs no LDS staging; the adds wrap, so any split of the d range gives the same bits.  With
 //     few GLWEs (one GLWE at N = 256, k = 4 is 1,280 outputs = 5 workgroups) the d range is split over `part`
@@ -27,58 +28,12 @@
 
 #include "keyswitch_launch.hpp"
 #include "ks_device.hpp"
+#include "pks_rotate.hpp"
 
 namespace mi {
 namespace ks {
 
 using u64 = uint64_t;
-
-struct RotShape {
-  uint32_t n_g;       // GLWEs of this launch
-  uint32_t per;       // rows of T per GLWE
-  uint32_t cnt_last;  // ciphertexts of the last GLWE (the others hold `per`)
-  uint32_t d0;        // degree of a GLWE's first row (non-zero when one GLWE is summed piecewise)
-  uint32_t log_n, out_size;  // N = 2^log_n, (k + 1) N words per row
-  uint32_t wb;        // workgroups of 256 words per row
-  uint32_t dl, part;  // rows per slice of the d range, slices per GLWE
-  uint32_t accumulate;  // add to the output instead of overwriting it
-};
-
-// grid.x = n_g * wb, grid.y = part.  dst: the output GLWEs (part == 1) or the partial sums [g][slice][word].
-__global__ __launch_bounds__(256) void pks_rotate_sum_kernel(u64* __restrict__ dst, const u64* __restrict__ t,
-                                                             RotShape s) {
-  const uint32_t g = blockIdx.x / s.wb, w = (blockIdx.x % s.wb) * 256 + threadIdx.x, slice = blockIdx.y;
-  if (w >= s.out_size) return;
-  const uint32_t n_mask = (1u << s.log_n) - 1u, j = w & n_mask;
-  const uint32_t cnt = g + 1 == s.n_g ? s.cnt_last : s.per;
-  const uint32_t lo = slice * s.dl, hi = min(cnt, lo + s.dl);
-  const u64* row = t + ((uint64_t)g * s.per + lo) * s.out_size + (w - j);  // polynomial p of row lo
-  u64 acc = 0;
-#pragma unroll 4
-  for (uint32_t d = lo; d < hi; ++d, row += s.out_size) {
-    const uint32_t deg = s.d0 + d;  // < N: lwe_per_glwe <= N
-    const u64 v = row[(j - deg) & n_mask];
-    acc += j < deg ? (u64)0 - v : v;
-  }
-  if (s.part == 1) {
-    u64* o = dst + (uint64_t)g * s.out_size + w;
-    *o = s.accumulate ? *o + acc : acc;
-  } else {
-    dst[((uint64_t)g * s.part + slice) * s.out_size + w] = acc;
-  }
-}
-
-// out[g][w] (+)= sum over the slices of partial[g][slice][w]; grid.x = n_g * wb
-__global__ __launch_bounds__(256) void pks_reduce_kernel(u64* __restrict__ out, const u64* __restrict__ partial,
-                                                         RotShape s) {
-  const uint32_t g = blockIdx.x / s.wb, w = (blockIdx.x % s.wb) * 256 + threadIdx.x;
-  if (w >= s.out_size) return;
-  const u64* p = partial + (uint64_t)g * s.part * s.out_size + w;
-  u64* o = out + (uint64_t)g * s.out_size + w;
-  u64 acc = s.accumulate ? *o : 0;
-  for (uint32_t q = 0; q < s.part; ++q) acc += p[(uint64_t)q * s.out_size];
-  *o = acc;
-}
 
 // packed[b][i], i < words: bits [64 i, 64 i + 64) of the little-end-first concatenation of the `count` values
 // modulus_switch(glwe[b][j], log_mod), log_mod bits each
@@ -119,10 +74,10 @@ __global__ __launch_bounds__(256) void glwe_extract_kernel(u64* __restrict__ glw
 
 static constexpr size_t PKS_MAX_ROWS = (size_t)1 << 21;  // rows of one GEMM launch (its batch bound is 2^22 - 1)
 
-PksPlan pks_plan(const KsGeometry& g, size_t n_lwe, size_t lwe_per_glwe) {
+PksPlan pks_plan_rows(size_t out_size, size_t word_bytes, size_t n_lwe, size_t lwe_per_glwe) {
   PksPlan p;
   if (n_lwe == 0) return p;
-  const size_t row_bytes = g.out_size * 8, n_glwe = (n_lwe + lwe_per_glwe - 1) / lwe_per_glwe;
+  const size_t row_bytes = out_size * word_bytes, n_glwe = (n_lwe + lwe_per_glwe - 1) / lwe_per_glwe;
   size_t n_g, per;  // GLWEs and rows per GLWE of the largest rotate-and-sum launch
   if (lwe_per_glwe * row_bytes <= PKS_ROW_CAP_BYTES) {
     n_g = PKS_ROW_CAP_BYTES / (lwe_per_glwe * row_bytes);
@@ -139,71 +94,30 @@ PksPlan pks_plan(const KsGeometry& g, size_t n_lwe, size_t lwe_per_glwe) {
   }
   if (p.rows > n_lwe) p.rows = n_lwe;
   // split the d range until the launch has ~1024 workgroups, slices of at least 8 rows
-  const size_t blocks = n_g * ((g.out_size + 255) / 256);
+  const size_t blocks = n_g * ((out_size + 255) / 256);
   size_t part = (1024 + blocks - 1) / blocks;
   if (part > (per + 7) / 8) part = (per + 7) / 8;
   const size_t dl = (per + part - 1) / part;
   p.part = (per + dl - 1) / dl;
   p.t_bytes = p.rows * row_bytes;
-  p.digit_bytes = ks_digit_bytes(g, p.rows);
   p.partial_bytes = p.part > 1 ? n_g * p.part * row_bytes : 0;
   return p;
 }
 
-static hipError_t rotate_sum(uint64_t* out, const uint64_t* t, uint64_t* partials, ks::RotShape s, hipStream_t st) {
-  s.dl = (s.per + s.part - 1) / s.part;
-  const dim3 grid1(s.n_g * s.wb, s.part);
-  hipLaunchKernelGGL(ks::pks_rotate_sum_kernel, grid1, dim3(256), 0, st, s.part == 1 ? out : partials, t, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || s.part == 1) return e;
-  hipLaunchKernelGGL(ks::pks_reduce_kernel, dim3(s.n_g * s.wb), dim3(256), 0, st, out, partials, s);
-  return hipGetLastError();
+PksPlan pks_plan(const KsGeometry& g, size_t n_lwe, size_t lwe_per_glwe) {
+  PksPlan p = pks_plan_rows(g.out_size, 8, n_lwe, lwe_per_glwe);
+  if (n_lwe != 0) p.digit_bytes = ks_digit_bytes(g, p.rows);
+  return p;
 }
 
 hipError_t launch_packing_keyswitch(uint64_t* glwe_out, const uint64_t* lwe_in, const void* frag, void* t, void* digits,
                                     void* partials, size_t n_lwe, size_t lwe_per_glwe, size_t polynomial_size,
                                     const KsGeometry& g, const PksPlan& plan, hipStream_t st) {
-  if (n_lwe == 0) return hipSuccess;
-  const size_t lwe_size = g.in_dim + 1, n_glwe = (n_lwe + lwe_per_glwe - 1) / lwe_per_glwe;
-  ks::RotShape s;
-  s.log_n = (uint32_t)__builtin_ctzll(polynomial_size);
-  s.out_size = (uint32_t)g.out_size;
-  s.wb = (uint32_t)((g.out_size + 255) / 256);
-  s.part = (uint32_t)plan.part;
-  s.dl = 0;
-  uint64_t* tw = (uint64_t*)t;
-  if (!plan.piecewise) {  // whole GLWEs per chunk
-    const size_t gpc = (plan.rows + lwe_per_glwe - 1) / lwe_per_glwe;
-    for (size_t g0 = 0; g0 < n_glwe; g0 += gpc) {
-      const size_t first = g0 * lwe_per_glwe, rows = n_lwe - first < gpc * lwe_per_glwe ? n_lwe - first : gpc * lwe_per_glwe;
-      hipError_t e = launch_keyswitch(tw, lwe_in + first * lwe_size, frag, digits, rows, g, st);
-      if (e != hipSuccess) return e;
-      s.n_g = (uint32_t)((rows + lwe_per_glwe - 1) / lwe_per_glwe);
-      s.per = (uint32_t)lwe_per_glwe;
-      s.cnt_last = (uint32_t)(rows - (size_t)(s.n_g - 1) * lwe_per_glwe);
-      s.d0 = 0;
-      s.accumulate = 0;
-      e = rotate_sum(glwe_out + g0 * g.out_size, tw, (uint64_t*)partials, s, st);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  for (size_t gi = 0; gi < n_glwe; ++gi) {  // one GLWE's rows exceed the cap: pieces of plan.rows rows
-    const size_t first = gi * lwe_per_glwe, cnt = n_lwe - first < lwe_per_glwe ? n_lwe - first : lwe_per_glwe;
-    for (size_t d0 = 0; d0 < cnt; d0 += plan.rows) {
-      const size_t rows = cnt - d0 < plan.rows ? cnt - d0 : plan.rows;
-      hipError_t e = launch_keyswitch(tw, lwe_in + (first + d0) * lwe_size, frag, digits, rows, g, st);
-      if (e != hipSuccess) return e;
-      s.n_g = 1;
-      s.per = (uint32_t)plan.rows;  // the slices the partial sums were sized for
-      s.cnt_last = (uint32_t)rows;
-      s.d0 = (uint32_t)d0;
-      s.accumulate = d0 != 0;
-      e = rotate_sum(glwe_out + gi * g.out_size, tw, (uint64_t*)partials, s, st);
-      if (e != hipSuccess) return e;
-    }
-  }
-  return hipSuccess;
+  const size_t lwe_size = g.in_dim + 1;
+  return ks::pks_run<uint64_t>(glwe_out, (uint64_t*)t, (uint64_t*)partials, n_lwe, lwe_per_glwe, polynomial_size,
+                               g.out_size, plan, st, [&](size_t first, size_t rows) {
+                                 return launch_keyswitch(t, lwe_in + first * lwe_size, frag, digits, rows, g, st);
+                               });
 }
 
 size_t glwe_compressed_words(size_t polynomial_size, int glwe_dim, size_t bodies_count, int log_modulus) {

@@ -28,9 +28,10 @@
 // reference's skip (bootstrap.rs:100) changes no value.
 //
 // Out of scope here: non-native power-of-two moduli below 2^128 (the closest_representable step of blind_rotate_u128,
-// bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the noise-squashing
-// packing keyswitch (base_log 61 over u128), the C++ mirror, the serialised Fourier128LweBootstrapKey format (transform
-// output of the reference's own FFT: no meaning here), and fusing the passes (mac into the transforms is the follow-up).
+// bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the C++ mirror, the
+// serialised Fourier128LweBootstrapKey format (transform output of the reference's own FFT: no meaning here), and fusing
+// the passes (mac into the transforms is the follow-up).  The noise-squashing packing keyswitch (base_log 61 over u128)
+// is packing_keyswitch128.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -15,7 +15,9 @@ package never imports it.  Reference paths relative to /root/reference/tfhe/src/
 
 The reference's transform is tfhe-fft's measured plan (tfhe-fft/src/unordered.rs:654-940); ``np.fft`` computes
 the same DFT (exp(-2 pi i / n) forward kernel, 1/n on the inverse) with different f64 rounding, so this oracle
-pins the algorithm and its error bound, not bit patterns (parity is decryption-only).
+pins the algorithm and its error, not bit patterns (SURVEY.md §8f rank 4 calls the parity decryption-only; since
+then the engines' error is measured against this restatement's own, both taken against a long-double transform,
+tests/fft_accuracy.py, and the conversions at both ends are pinned bit for bit, tests/torus_corners.py).
 Fourier arrays here are in natural frequency order.
 """
 from __future__ import annotations
@@ -52,13 +54,20 @@ def forward_as_integer(x) -> np.ndarray:
     return np.fft.fft(z * twisties(m), axis=-1)
 
 
+def _round_half_away(x) -> np.ndarray:
+    """f64::round: ties away from zero (np.round ties to even).  x - trunc(x) is exact."""
+    t = np.trunc(x)
+    return t + np.where(np.abs(x - t) >= 0.5, np.copysign(1.0, x), 0.0)
+
+
 def from_torus(x) -> np.ndarray:
     """fract = x - round(x); round(fract * 2^64) as i64 (saturating, as Rust's `as`) as u64."""
     x = np.asarray(x, dtype=np.float64)
-    fr = x - np.round(x)
-    v = np.round(fr * TWO64)
+    fr = x - _round_half_away(x)
+    v = _round_half_away(fr * TWO64)
     v = np.clip(v, -9223372036854775808.0, 9223372036854775807.0)
-    out = np.where(v >= 9223372036854775807.0, np.int64(2**63 - 1), v.astype(np.int64))
+    top = v >= 9223372036854775807.0
+    out = np.where(top, np.int64(2**63 - 1), np.where(top, 0.0, v).astype(np.int64))
     return out.view(U64)
 
 

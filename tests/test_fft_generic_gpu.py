@@ -14,6 +14,7 @@ import pytest
 
 import fft_oracle as F
 import tfhe_helpers as H
+from fft_accuracy import exact_ext_product as _exact_ext_product, exact_products as _exact_products  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -83,49 +84,6 @@ def test_generic_transforms(engine, n):
     fft.add_backward_as_torus(acc, four)
     with np.errstate(over="ignore"):
         assert F.signed_diff(host(acc), base + x).max() < bound
-
-
-def _signed_mod_p(u):
-    """two's complement u64 (small signed values) -> residues mod p"""
-    s = u.view(np.int64)
-    return np.where(s < 0, (np.uint64(P) - (np.uint64(0) - u)), u).astype(np.uint64)
-
-
-def _exact_products(oracle, a, d, base_log):
-    """a (..., N) u64 times d (..., N) small signed digits (two's complement), negacyclic mod 2^64, exact.  Through
-    the oracle's Solinas transform with 32-bit limbs of a when N 2^32 2^(B-1) < p / 2, by rotation sums otherwise."""
-    n = a.shape[-1]
-    if n.bit_length() - 1 + base_log < 31:
-        plan = oracle.Plan.try_new(n, P)
-        flat_a = np.ascontiguousarray(a.reshape(-1, n))
-        d_hat = plan.fwd(np.ascontiguousarray(_signed_mod_p(d.reshape(-1, n))), threads=16)
-        out = np.zeros_like(flat_a)
-        with np.errstate(over="ignore"):
-            for t in range(2):
-                limb = (flat_a >> np.uint64(32 * t)) & np.uint64(0xFFFFFFFF)
-                v = plan.inv(plan.mul_assign_normalize(plan.fwd(limb, threads=16), d_hat), threads=16)
-                v = np.where(v > np.uint64(P // 2), v - np.uint64(P), v)
-                out += v << np.uint64(32 * t)
-        return out.reshape(a.shape)
-    out = np.zeros(a.reshape(-1, n).shape, np.uint64)
-    fa, fd = a.reshape(-1, n), d.reshape(-1, n)
-    with np.errstate(over="ignore"):
-        for i in range(fa.shape[0]):
-            for j in range(n):
-                if fd[i, j]:
-                    out[i] += fd[i, j] * np.concatenate([np.uint64(0) - fa[i, n - j:], fa[i, : n - j]])
-    return out.reshape(a.shape)
-
-
-def _exact_ext_product(oracle, glwe, ggsw, base_log, level):
-    """sum over levels li and rows r of digit_li(glwe[r]) x ggsw[li][r][c], exact in Z_2^64[X]/(X^N + 1)"""
-    kp1, n = glwe.shape
-    terms = F.decompose(glwe, base_log, level)  # least significant level first
-    a = np.stack([np.broadcast_to(ggsw[li, r], (kp1, n)) for li in range(level) for r in range(kp1)])
-    d = np.stack([np.broadcast_to(terms[li][r], (kp1, n)) for li in range(level) for r in range(kp1)])
-    prods = _exact_products(oracle, np.ascontiguousarray(a), np.ascontiguousarray(d), base_log)
-    with np.errstate(over="ignore"):
-        return prods.sum(axis=0, dtype=np.uint64)
 
 
 @pytest.mark.parametrize("n,k,base_log,level", [

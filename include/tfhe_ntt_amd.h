@@ -305,9 +305,11 @@ int mi_sample_extract_batch(uint64_t *lwe_out, const uint64_t *glwe, size_t poly
 
 /* ---- Scratch pool (no reference counterpart: the reference's PodStack / ComputationBuffers) -----------------------
  * Batched entry points that need temporary device memory take it from a per-device pool of blocks kept for reuse,
- * ordered by events (a block is reissued only behind the last kernel that used it, on any stream; no call blocks the
- * host).  _trim frees the idle blocks of `device` (-1: every device) once their last users retired; _bytes reports
- * what the pool holds. */
+ * ordered by events (a block is reissued only behind the last kernel that used it, on any stream; a call that reuses a
+ * pooled block never blocks the host).  A call whose request no idle block fits grows the pool and does block: it
+ * allocates a new block and first frees the idle blocks too small for it, each after its last user has retired.  _trim
+ * frees the idle blocks of `device` (-1: every device) once their last users retired; _bytes reports what the pool
+ * holds. */
 int mi_scratch_trim(int device, size_t *released);
 int mi_scratch_bytes(int device, size_t *bytes);
 

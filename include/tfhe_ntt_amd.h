@@ -699,9 +699,10 @@ int mi_glwe_extract_batch(uint64_t *glwe, const uint64_t *packed, size_t polynom
  * ggsw.rs:517-567; the exact negacyclic product).  Every u128 crosses this ABI as two little-endian u64 words (lo, hi),
  * as mi_native_polymul_batch takes them; u128 buffers are 16-byte aligned device pointers.
  * Not provided: non-native power-of-two moduli below 2^128 (the closest_representable step of blind_rotate_u128,
- * bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the C++ mirror,
+ * bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the C++ mirror,
  * and the serialised Fourier128LweBootstrapKey format (it holds the output of the reference's own FFT and has no
- * meaning here).  The packing keyswitch and the compression of its results are the next section.
+ * meaning here).  The multi-bit variant follows the classic entries; the packing keyswitch and the compression of
+ * its results are the next section.
  *
  * mi_pbs128_limb_plan (no reference counterpart, needs no device): limb_bits = the largest w with
  * R N 2^(base_log - 1) (2^w - 1) <= (p - 1) / 2, R = (k + 1) level, p = 2^64 - 2^32 + 1; n_limbs = ceil(128 / w)
@@ -749,6 +750,58 @@ int mi_blind_rotate128_batch(const mi_pbs128_key *key, uint64_t *acc_glwe, const
  * lwe_out[b] = k polynomial_size + 1 u128. */
 int mi_pbs128_batch(const mi_pbs128_key *key, uint64_t *lwe_out, const uint64_t *lwe_in, const uint64_t *lut,
                     size_t batch, int ms_mode, void *stream);
+/* The multi-bit 128-bit bootstrap (algorithms/lwe_multi_bit_programmable_bootstrapping.rs:
+ * multi_bit_programmable_bootstrap_f128_lwe_ciphertext, multi_bit_f128_deterministic_blind_rotate_assign,
+ * prepare_multi_bit_fourier_128_ggsw_mem_optimized :2257-2700; the std_* forms :1849-2255 build the bundle in the
+ * standard domain), what V1_3_NOISE_SQUASHING_PARAM_GPU_MULTI_BIT_GROUP_4_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M128 runs
+ * (k = 2, N = 2048, base 2^23, 3 levels, grouping factor 4, native u128;
+ * shortint/parameters/v1_3/noise_squashing/p_fail_2_minus_128/mod.rs:65-77).  Exact as the classic entries above: bit
+ * for bit the integer arithmetic mod 2^128 of
+ *   acc /= X^ms(body);  per group: bundle = G_0 + sum_idx X^(d_idx) G_idx,  acc <- 0 + bundle (.) acc  (not a CMUX),
+ * d_idx = the standard switch to log2(2N) bits of the wrapping sum of the group's mask elements that idx selects,
+ * idx = 1 .. 2^g - 1 (StandardMultiBitModulusSwitchedCt: the sum is switched, not each element), SignedDecomposer<u128>
+ * as above.  The bundle is never formed: X^d is a pointwise factor in the transform domain, so a step is one
+ * multiply-accumulate over the 2^g GGSWs of the group.
+ * Not provided: non-native moduli, a LUT index per item, the C++ mirror, and the serialised
+ * Fourier128LweMultiBitBootstrapKey format.
+ *
+ * mi_pbs128_multi_bit_limb_plan (no reference counterpart, needs no device): a column now sums 2^g GGSWs, so limb_bits
+ * = the largest w with 2^g R N 2^(base_log - 1) (2^w - 1) <= (p - 1) / 2, R = (k + 1) level; n_limbs = ceil(128 / w)
+ * (w = 22, 6 limbs at the shape above).  grouping_factor outside {2, 3, 4} is MI_ERR_INVALID_ARG; the other argument
+ * rules and the outputs are those of mi_pbs128_limb_plan, which it leaves as it is.  MI_ERR_UNSUPPORTED when n_limbs >
+ * 32: the width is up to 4 bits below the classic one, so 32 limbs here are the 16 of mi_pbs128_limb_plan and every
+ * shape that has a classic key has a multi-bit one (base 2^42, 3 levels, k = 1, N = 2048, g = 2: 22 limbs of 6 bits). */
+int mi_pbs128_multi_bit_limb_plan(size_t polynomial_size, int k, int base_log, int level, int grouping_factor,
+                                  int *limb_bits, int *n_limbs);
+/* The multi-bit bootstrap key.  bsk_std: the reference's LweMultiBitBootstrapKey<u128> in standard form as a device
+ * pointer: n_lwe / g groups of 2^g GGSWs, group-major, each GGSW in the level, row and polynomial layout
+ * mi_pbs128_key_create takes; GGSW idx of group i encrypts prod_m (s[i g + m] XOR NOT bit_m(idx)), bit_m(idx) =
+ * (idx >> (g - 1 - m)) & 1, as documented for mi_fft64_multi_bit_pbs_key_create
+ * (lwe_multi_bit_bootstrap_key_generation.rs:398-421).  A private prepared copy is made on `stream`, which is
+ * synchronised, as mi_pbs128_key_create makes it (with the multi-bit limb width; in place, no second key-sized
+ * buffer), and with it the table of the 2N powers of the plan's 2N-th root (16 N bytes).  MI_ERR_INVALID_ARG for a
+ * NULL argument, a grouping factor outside {2, 3, 4}, n_lwe that is 0 or no multiple of it, and where
+ * mi_pbs128_limb_plan says so; MI_ERR_UNSUPPORTED for a plan that is not the Goldilocks plan of polynomial_size, k > 3
+ * and more than 32 limbs.  The key borrows `plan`, which must outlive it. */
+typedef struct mi_pbs128_multi_bit_key mi_pbs128_multi_bit_key;
+int mi_pbs128_multi_bit_key_create(const mi_ntt64_plan *plan, const uint64_t *bsk_std, size_t n_lwe, int k,
+                                   size_t polynomial_size, int base_log, int level, int grouping_factor,
+                                   void *stream, mi_pbs128_multi_bit_key **out_key);
+int mi_pbs128_multi_bit_key_destroy(mi_pbs128_multi_bit_key *key);
+int mi_pbs128_multi_bit_key_info(const mi_pbs128_multi_bit_key *key, size_t *n_lwe, int *k, size_t *polynomial_size,
+                                 int *base_log, int *level, int *grouping_factor, int *limb_bits, int *n_limbs);
+/* multi_bit_f128_deterministic_blind_rotate_assign (:2257-2700), batched and in place: acc_glwe[b] ((k + 1)
+ * polynomial_size u128) is divided by X^ms(body) and taken through the n_lwe / g steps acc <- bundle (.) acc.
+ * lwe_in[b]: n_lwe + 1 u64 at the native 2^64 modulus, switched on the device (there is no ms_mode, as in the f64
+ * multi-bit entries).  Async on `stream`, stream-ordered scratch, chunked as mi_blind_rotate128_batch
+ * (MI_PBS128_CHUNK); batch = 0 is MI_OK.  The buffers of a call are disjoint (overlapping ones are
+ * MI_ERR_INVALID_ARG and nothing is written). */
+int mi_pbs128_multi_bit_blind_rotate_batch(const mi_pbs128_multi_bit_key *key, uint64_t *acc_glwe,
+                                           const uint64_t *lwe_in, size_t batch, void *stream);
+/* multi_bit_programmable_bootstrap_f128_lwe_ciphertext over a batch: that rotation of the one shared LUT GLWE `lut`,
+ * then extract_lwe_sample_from_glwe_ciphertext at degree 0: lwe_out[b] = k polynomial_size + 1 u128. */
+int mi_pbs128_multi_bit_batch(const mi_pbs128_multi_bit_key *key, uint64_t *lwe_out, const uint64_t *lwe_in,
+                              const uint64_t *lut, size_t batch, void *stream);
 
 /* ---- The 128-bit packing keyswitch and compression of noise squashing ---------------------------------------------
  * What shortint does with the u128 LWEs of the bootstrap above: compress_noise_squashed_ciphertexts_into_list
@@ -759,8 +812,8 @@ int mi_pbs128_batch(const mi_pbs128_key *key, uint64_t *lwe_out, const uint64_t 
  * 21-32): base 2^61, 1 level, k = 6, N = 1024, 128 LWEs per GLWE, native u128 modulus, input LWE dimension 4096.
  * Integer-only and bit-exact; every u128 is two little-endian u64 words (lo, hi), u128 buffers are 16-byte aligned
  * device pointers, as in the section above.
- * Not provided: sample extraction of u128 LWEs at a monomial degree (the list's unpack, a client-side step), the
- * multi-bit 128-bit bootstrap, non-native u128 moduli, the C++ mirror, serialised formats, and a digit pass fused into
+ * Not provided: sample extraction of u128 LWEs at a monomial degree (the list's unpack, a client-side step),
+ * non-native u128 moduli, the C++ mirror, serialised formats, and a digit pass fused into
  * the GEMM.
  *
  * mi_lwe_pksk128_create takes the reference's LwePackingKeyswitchKey<u128> layout as a device pointer: in_dim blocks

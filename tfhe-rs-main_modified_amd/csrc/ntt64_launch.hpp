@@ -194,6 +194,14 @@ hipError_t launch_ext_product128(bool cmux, uint64_t* out, uint64_t* glwe, const
 hipError_t launch_blind_rotate128(uint64_t* lwe_out, uint64_t* acc_glwe, const uint64_t* lut, const uint64_t* lwe_in,
                                   const uint64_t* key, size_t n_lwe, size_t batch, int centered, int pre,
                                   const Pbs128Shape& p, const Ntt128Route& rt, hipStream_t s);
+// pbs128_multi_bit.hip — the multi-bit blind rotation over the n_lwe / grouping_factor groups of 2^grouping_factor
+// prepared GGSWs at `key` (launch_pbs128_key_prepare with the multi-bit limb width); roots = the 2N powers psi^j of the
+// plan's 2N-th root on the device.  lwe_out / acc_glwe / lut as launch_blind_rotate128; lwe_in: native u64 LWEs, switched
+// here with the standard switch of each subset sum
+hipError_t launch_multi_bit_blind_rotate128(uint64_t* lwe_out, uint64_t* acc_glwe, const uint64_t* lut,
+                                            const uint64_t* lwe_in, const uint64_t* key, const uint64_t* roots,
+                                            size_t n_lwe, int grouping_factor, size_t batch, const Pbs128Shape& p,
+                                            const Ntt128Route& rt, hipStream_t s);
 
 }  // namespace mi
 // (keyswitch.hip's entry points: keyswitch_launch.hpp)

@@ -36,8 +36,8 @@
 // pks_rotate.hpp's at W = u128.  glwe_compress128_kernel / glwe_extract128_kernel: PackedIntegers<u128> packs into
 // 128-bit words; as (lo, hi) u64 pairs that is the bit string the u64 packer writes, rounded up to an even word count.
 //
-// Out of scope here: sample extraction of u128 LWEs at a monomial degree (the list's unpack, a client-side step), the
-// multi-bit 128-bit bootstrap, non-native u128 moduli, the C++ mirror header, serialised formats, and fusing the
+// Out of scope here: sample extraction of u128 LWEs at a monomial degree (the list's unpack, a client-side step),
+// non-native u128 moduli, the C++ mirror header, serialised formats, and fusing the
 // digit pass into the GEMM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

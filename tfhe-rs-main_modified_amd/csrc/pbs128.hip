@@ -28,83 +28,20 @@
 // reference's skip (bootstrap.rs:100) changes no value.
 //
 // Out of scope here: non-native power-of-two moduli below 2^128 (the closest_representable step of blind_rotate_u128,
-// bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the multi-bit 128-bit variant, the C++ mirror, the
+// bootstrap.rs:217-231), u32 / u128 input LWEs, a LUT index per item, the C++ mirror, the
 // serialised Fourier128LweBootstrapKey format (transform output of the reference's own FFT: no meaning here), and fusing
 // the passes (mac into the transforms is the follow-up).  The noise-squashing packing keyswitch (base_log 61 over u128)
-// is packing_keyswitch128.hip.
+// is packing_keyswitch128.hip; the multi-bit 128-bit bootstrap is pbs128_multi_bit.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "scratch.hpp"
-#include "mi_arith.hpp"
-#include "ntt64_launch.hpp"
-#include "pbs_device.hpp"
-#include "pbs_passes.hpp"
+#include "pbs128_device.hpp"
 
 namespace mi {
 namespace pbs128 {
-
-using pbs::P;
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
-struct Shape {
-  uint32_t logn, n, k, level, limb_bits, n_limbs;
-  int base_log;
-};
-
-// u128 values are two little-endian u64 words (lo, hi), 16-byte aligned: element i at p + 2 i
-__device__ __forceinline__ u128 ld128(const u64* p, uint64_t i) {
-  const u64x2 v = *reinterpret_cast<const u64x2*>(p + 2 * i);
-  return (u128)v.x | ((u128)v.y << 64);
-}
-__device__ __forceinline__ void st128(u64* p, uint64_t i, u128 v) {
-  const u64x2 w = {(u64)v, (u64)(v >> 64)};
-  *reinterpret_cast<u64x2*>(p + 2 * i) = w;
-}
-
-// SignedDecomposer<u128>::init_decomposer_state (decomposer.rs:156-185); rep = base_log * level in [1, 127], so the
-// shifts and the balancing bit span both words
-__device__ __forceinline__ u128 decomp_init(u128 input, unsigned rep) {
-  u128 res = input >> (128u - rep - 1u);
-  const u128 rounding_bit = res & 1u;
-  res += 1;
-  res >>= 1;
-  res &= ~(u128)0 >> (128u - rep);
-  const u128 need_balance = (((res - 1) | (rounding_bit << (rep - 1))) & res) >> (rep - 1);
-  return res - (need_balance << rep);
-}
-
-// decompose_one_level (iter.rs:131-151) at Scalar = u128 (what collect_next_term_split_scalar, ggsw.rs:517-567, computes
-// on split words); the digit lies in [-2^(B-1), 2^(B-1)] and B <= 58 wherever a limb plan exists, so it fits an i64
-__device__ __forceinline__ int64_t decomp_next(int base_log, u128& state) {
-  const u128 mask = ((u128)1 << base_log) - 1;
-  const u128 res = state & mask;
-  state = (u128)((i128)state >> base_log);
-  const u128 carry = (((res - 1) | state) & res) >> (base_log - 1);
-  state += carry;
-  return (int64_t)(u64)(res - (carry << base_log));
-}
-
-// the `level` digits of x as canonical residues, least significant level first: dst[li * level_stride]
-__device__ __forceinline__ void decompose_store(u128 x, u64* __restrict__ dst, uint64_t level_stride, int base_log,
-                                                int level) {
-  u128 state = decomp_init(x, (unsigned)(base_log * level));
-  for (int li = 0; li < level; ++li) {
-    const int64_t d = decomp_next(base_log, state);
-    dst[(uint64_t)li * level_stride] = d < 0 ? P + (u64)d : (u64)d;
-  }
-}
-
-// the switched value in [0, 2N) of an input word: the u64 paths' modulus_switch (fft_impl/common.rs:10-23), or the word
-// itself when the caller switched already (MI_MS_PRE_SWITCHED)
-__device__ __forceinline__ uint32_t switched(u64 raw, unsigned log_mod, int pre) {
-  return (uint32_t)(pre ? raw : pbs::modulus_switch(raw, log_mod)) & ((1u << log_mod) - 1u);
-}
 
 // key preparation, first half: limb j of every coefficient of `n_polys` standard-domain u128 polynomials,
 // dst[(poly n_limbs + j) N + e] = (g >> (w j)) mod 2^w
@@ -175,24 +112,7 @@ __global__ __launch_bounds__(256) void rotate_decompose(u64* __restrict__ digits
 // y[b][c][j][e] = sum_r digits[b][r][e] . key[r][c][j][e] mod p over the R = level (k + 1) rows of the step's prepared
 // GGSW (N^-1 folded in).  One thread per coefficient and item: each digit is read once and the KP1 * NL sums stay in
 // registers.  Grid: x over the coefficients, y over the items.
-// One sum of the mac: Goldilocks::add of Goldilocks::mul per term, or (WIDE) the terms' 128-bit products summed in
-// pbs_device.hpp's Acc128 and reduced once at the end — 9 registers per sum instead of 2, so only where the
-// KP1 * NL sums of a thread still fit (the production shape's 18 do).  Both give the canonical residue of the sum.
-template <bool WIDE>
-struct MacSum;
-template <>
-struct MacSum<false> {
-  u64 v = 0;
-  __device__ __forceinline__ void mac(u64 x, u64 w) { v = Goldilocks::add(v, Goldilocks::mul(x, w)); }
-  __device__ __forceinline__ u64 value() const { return v; }
-};
-template <>
-struct MacSum<true> {
-  pbs::Acc128 a;
-  __device__ __forceinline__ void mac(u64 x, u64 w) { a.mac(x, w); }
-  __device__ __forceinline__ u64 value() const { return a.value(0); }
-};
-
+// One sum of the mac: MacSum (pbs128_device.hpp), the wide form where the KP1 * NL sums of a thread fit.
 template <int KP1, int NL>
 __global__ __launch_bounds__(256) void mac(u64* __restrict__ y, const u64* __restrict__ digits,
                                            const u64* __restrict__ ggsw, uint32_t batch, Shape sh) {
@@ -221,14 +141,17 @@ __global__ __launch_bounds__(256) void mac(u64* __restrict__ y, const u64* __res
 }
 
 // out[b][c][e] += sum_j v_j 2^(w j) mod 2^128, v_j = y[b][c][j][e] taken as v - p when v > (p - 1) / 2 (the exact
-// integer limb sum): two-word wrapping arithmetic with explicit carries
+// integer limb sum): two-word wrapping arithmetic with explicit carries.  ADD false: out = that sum (the destination of
+// the multi-bit step starts from zero)
+template <bool ADD>
 __global__ __launch_bounds__(256) void recombine(u64* __restrict__ out, const u64* __restrict__ y, uint32_t batch,
                                                  Shape sh) {
   const uint64_t total = (uint64_t)(sh.k + 1) * sh.n * batch;
   for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t poly = i >> sh.logn, e = i & (sh.n - 1);
     const u64* v = y + ((poly * sh.n_limbs) << sh.logn) + e;
-    u64x2 acc = *reinterpret_cast<const u64x2*>(out + 2 * i);
+    u64x2 acc = {0, 0};
+    if (ADD) acc = *reinterpret_cast<const u64x2*>(out + 2 * i);
     for (uint32_t j = 0; j < sh.n_limbs; ++j) {
       const u64 r = __builtin_nontemporal_load(v + ((uint64_t)j << sh.logn));
       const int64_t sv = (int64_t)(r > (P - 1) / 2 ? r - P : r);  // |sv| < 2^63
@@ -265,19 +188,6 @@ __global__ __launch_bounds__(256) void extract(u64* __restrict__ lwe_out, const 
   }
 }
 
-inline Shape shape_of(const Pbs128Shape& p) {
-  return Shape{(uint32_t)p.logn, 1u << p.logn, (uint32_t)p.k, (uint32_t)p.level, (uint32_t)p.limb_bits,
-               (uint32_t)p.n_limbs, p.base_log};
-}
-
-// the plan's transform over `batch` contiguous polynomials (the routing of mi_ntt64_fwd_batch / mi_ntt64_inv_batch)
-inline hipError_t ntt(bool fwd, const Ntt128Route& r, u64* d, size_t batch, hipStream_t s) {
-  const size_t n = (size_t)1 << r.logn;
-  if (r.twisted) return launch_ntt_tw(fwd, d, batch, n, fwd ? r.twist_f : r.twist_i, s);
-  if (r.split) return launch_ntt_split(fwd, r.logn, d, batch, n, fwd ? r.tw : r.itw, r.st, s);
-  return launch_ntt(fwd, r.logn, true, MontParams{}, d, batch, n, fwd ? r.tw : r.itw, s);
-}
-
 template <int KP1>
 static hipError_t launch_mac_k(u64* y, const u64* digits, const u64* ggsw, uint32_t nb, const Shape& sh,
                                hipStream_t s) {
@@ -302,23 +212,6 @@ static hipError_t launch_mac(u64* y, const u64* digits, const u64* ggsw, uint32_
   }
 }
 
-// u64 words of one chunk item: its digits and limb products (+ its accumulator and body correction when `rotation`)
-inline size_t item_words(const Shape& sh, bool rotation) {
-  const size_t per = (size_t)(sh.k + 1) * sh.n;
-  return per * sh.level + per * sh.n_limbs + (rotation ? 2 * per + 1 : 0);
-}
-
-// ciphertexts per chunk: chunk_items of the item's scratch.  MI_PBS128_CHUNK, read on every call, lowers the bound (the
-// tests force two chunks with it)
-inline size_t chunk_size(const Shape& sh, size_t batch, bool rotation) {
-  size_t chunk = chunk_items(item_words(sh, rotation) * sizeof(u64), batch);
-  if (const char* v = std::getenv("MI_PBS128_CHUNK")) {
-    const long long c = std::atoll(v);
-    if (c >= 1) chunk = std::min<size_t>(chunk, (size_t)c);
-  }
-  return chunk;
-}
-
 // transform, mac, inverse, recombine of `nb` items whose digits are written: out += GGSW (.) (the decomposed input)
 static hipError_t product_tail(u64* out, u64* digits, u64* y, const u64* ggsw, uint32_t nb, const Shape& sh,
                                const Ntt128Route& rt, hipStream_t s) {
@@ -327,7 +220,32 @@ static hipError_t product_tail(u64* out, u64* digits, u64* y, const u64* ggsw, u
   if (e == hipSuccess) e = launch_mac(y, digits, ggsw, nb, sh, s);
   if (e == hipSuccess) e = ntt(false, rt, y, (size_t)nb * kp1 * sh.n_limbs, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(recombine, dim3(blocks_for((uint64_t)nb * kp1 * sh.n)), dim3(256), 0, s, out, y, nb, sh);
+  hipLaunchKernelGGL(recombine<true>, dim3(blocks_for((uint64_t)nb * kp1 * sh.n)), dim3(256), 0, s, out, y, nb, sh);
+  return hipGetLastError();
+}
+
+hipError_t launch_decompose(u64* digits, const u64* glwe, uint32_t nb, const Shape& sh, hipStream_t s) {
+  hipLaunchKernelGGL(glwe_decompose<false>, dim3(blocks_for((uint64_t)nb * (sh.k + 1) * sh.n)), dim3(256), 0, s, digits,
+                     const_cast<u64*>(glwe), (const u64*)nullptr, nb, sh);
+  return hipGetLastError();
+}
+
+hipError_t launch_init_acc(u64* acc, const u64* src, uint64_t src_stride, const u64* lwe_in, uint32_t n_lwe,
+                           uint32_t nb, const Shape& sh, hipStream_t s) {
+  hipLaunchKernelGGL(init_acc, dim3(blocks_for((uint64_t)nb * (sh.k + 1) * sh.n)), dim3(256), 0, s, acc, src, src_stride,
+                     lwe_in, (const u64*)nullptr, n_lwe, 0, nb, sh);
+  return hipGetLastError();
+}
+
+hipError_t launch_recombine_assign(u64* out, const u64* y, uint32_t nb, const Shape& sh, hipStream_t s) {
+  hipLaunchKernelGGL(recombine<false>, dim3(blocks_for((uint64_t)nb * (sh.k + 1) * sh.n)), dim3(256), 0, s, out, y, nb,
+                     sh);
+  return hipGetLastError();
+}
+
+hipError_t launch_extract(u64* lwe_out, const u64* acc, uint32_t nb, const Shape& sh, hipStream_t s) {
+  hipLaunchKernelGGL(extract, dim3(blocks_for((uint64_t)nb * ((uint64_t)sh.k * sh.n + 1))), dim3(256), 0, s, lwe_out,
+                     acc, nb, sh);
   return hipGetLastError();
 }
 

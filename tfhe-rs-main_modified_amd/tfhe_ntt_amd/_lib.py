@@ -181,6 +181,14 @@ _SIGS = {
     "mi_cmux128_batch": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "mi_blind_rotate128_batch": (_int, [_vp, _vp, _vp, _sz, _int, _vp]),
     "mi_pbs128_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _vp]),
+    "mi_pbs128_multi_bit_limb_plan": (_int, [_sz, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "mi_pbs128_multi_bit_key_create": (_int, [_vp, _vp, _sz, _int, _sz, _int, _int, _int, _vp, ctypes.POINTER(_vp)]),
+    "mi_pbs128_multi_bit_key_destroy": (_int, [_vp]),
+    "mi_pbs128_multi_bit_key_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_sz),
+                                            ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                            ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "mi_pbs128_multi_bit_blind_rotate_batch": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "mi_pbs128_multi_bit_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "mi_lwe_pksk128_create": (_int, [_vp, _sz, _int, _sz, _int, _int, _int, _vp, ctypes.POINTER(_vp)]),
     "mi_lwe_pksk128_destroy": (_int, [_vp]),
     "mi_lwe_pksk128_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_sz),

@@ -6,6 +6,9 @@ Reference (paths relative to /root/reference/tfhe/src/core_crypto):
 * ``blind_rotate_assign_split`` / ``blind_rotate_u128``  fft_impl/fft128_u128/crypto/bootstrap.rs:60-247
 * ``add_external_product_assign_split`` / ``cmux_split``  fft_impl/fft128_u128/crypto/ggsw.rs:17, :621-675
 
+* ``multi_bit_programmable_bootstrap_f128_lwe_ciphertext`` / ``multi_bit_f128_deterministic_blind_rotate_assign``
+  algorithms/lwe_multi_bit_programmable_bootstrapping.rs:2257-2700 (``mi_pbs128_multi_bit_*``, csrc/pbs128_multi_bit.hip)
+
 The reference multiplies with a double-double FFT; the engine runs exact limb products on the Goldilocks NTT
 (csrc/pbs128.hip), so every result equals plain integer arithmetic mod 2^128 bit for bit.  A u128 tensor is int64 (or
 uint64) storage with a trailing dimension of 2: the little-endian words (lo, hi).  The reference works on one
@@ -119,5 +122,73 @@ def programmable_bootstrap_f128_lwe_ciphertext(lwe_in, lwe_out, accumulator, key
     check(lib().mi_pbs128_batch(key._h, po, _lwe_in(key, lwe_in, batch), pl, batch, ms_mode, _stream(lwe_out)))
 
 
+def multi_bit_limb_plan(polynomial_size: int, glwe_dimension: int, base_log: int, level: int,
+                        grouping_factor: int) -> tuple[int, int]:
+    """(limb_bits, n_limbs) of the multi-bit limb split (``mi_pbs128_multi_bit_limb_plan``; needs no device): a column
+    sums the 2^g GGSWs of a group, so limb_bits is the largest w with
+    2^g (k + 1) level N 2^(base_log - 1) (2^w - 1) <= (p - 1) / 2, n_limbs = ceil(128 / w)."""
+    w, nl = ctypes.c_int(), ctypes.c_int()
+    check(lib().mi_pbs128_multi_bit_limb_plan(polynomial_size, glwe_dimension, base_log, level, grouping_factor,
+                                              ctypes.byref(w), ctypes.byref(nl)))
+    return w.value, nl.value
+
+
+class LweMultiBitBootstrapKey128:
+    """An ``LweMultiBitBootstrapKey<u128>`` prepared for the multi-bit 128-bit bootstrap (``mi_pbs128_multi_bit_key``).
+
+    ``bsk``: device tensor (n_lwe / g, 2^g, level, k + 1, k + 1, N, 2) in the reference's standard-domain layout:
+    group-major, GGSW ``idx`` of group i encrypting prod_m (s[i g + m] XOR NOT bit_m(idx)), each GGSW as
+    ``LweBootstrapKey128`` takes it.  A private prepared copy is made; ``bsk`` may be released afterwards."""
+
+    def __init__(self, bsk, base_log: int, level: int, grouping_factor: int, plan: Plan | None = None):
+        if (bsk.dim() != 7 or bsk.shape[1] != 1 << grouping_factor or bsk.shape[2] != level
+                or bsk.shape[3] != bsk.shape[4] or bsk.shape[6] != 2):
+            raise ValueError(f"assertion failed: bsk shape {tuple(bsk.shape)} != "
+                             f"(n_lwe / g, {1 << grouping_factor}, {level}, k + 1, k + 1, N, 2)")
+        self.grouping_factor = grouping_factor
+        self.input_lwe_dimension = int(bsk.shape[0]) * grouping_factor
+        self.glwe_dimension = int(bsk.shape[3]) - 1
+        self.polynomial_size = int(bsk.shape[5])
+        self.decomposition_base_log, self.decomposition_level_count = base_log, level
+        self.device = bsk.device
+        # kept alive with the key; by default the process-wide plan of Ntt64::new
+        self.plan = plan if plan is not None else Plan.cached(self.polynomial_size, SOLINAS_P, bsk.device.index or 0)
+        h = ctypes.c_void_p()
+        check(lib().mi_pbs128_multi_bit_key_create(self.plan.handle, _dev(bsk, "bsk"), self.input_lwe_dimension,
+                                                   self.glwe_dimension, self.polynomial_size, base_log, level,
+                                                   grouping_factor, _stream(bsk), ctypes.byref(h)))
+        self._h = h
+        w, nl = ctypes.c_int(), ctypes.c_int()
+        check(lib().mi_pbs128_multi_bit_key_info(h, None, None, None, None, None, None, ctypes.byref(w),
+                                                 ctypes.byref(nl)))
+        self.limb_bits, self.n_limbs = w.value, nl.value
+
+    def __del__(self):
+        release(self, "mi_pbs128_multi_bit_key_destroy")
+
+    def _glwe(self):
+        return (self.glwe_dimension + 1, self.polynomial_size)
+
+
+def multi_bit_blind_rotate_assign(key: LweMultiBitBootstrapKey128, acc, lwe_in) -> None:
+    """acc[b] /= X^ms(body), then the n_lwe / g steps acc <- bundle (.) acc over lwe_in[b] (u64, native modulus), in
+    place (multi_bit_f128_deterministic_blind_rotate_assign)."""
+    pa, batch = _u128(acc, "acc", key._glwe())
+    check(lib().mi_pbs128_multi_bit_blind_rotate_batch(key._h, pa, _lwe_in(key, lwe_in, batch), batch, _stream(acc)))
+
+
+def multi_bit_programmable_bootstrap_f128_lwe_ciphertext(lwe_in, lwe_out, accumulator,
+                                                         key: LweMultiBitBootstrapKey128) -> None:
+    """lwe_out[b] (k N + 1 u128) = the multi-bit PBS of lwe_in[b] (n_lwe + 1 u64) through the one shared LUT GLWE
+    ``accumulator`` ((k + 1, N, 2))."""
+    po, batch = _u128(lwe_out, "lwe_out", (key.glwe_dimension * key.polynomial_size + 1,))
+    pl, one = _u128(accumulator, "accumulator", key._glwe())
+    if one != 1:
+        raise ValueError("assertion failed: one accumulator is shared by the batch")
+    check(lib().mi_pbs128_multi_bit_batch(key._h, po, _lwe_in(key, lwe_in, batch), pl, batch, _stream(lwe_out)))
+
+
 __all__ = ["LweBootstrapKey128", "limb_plan", "add_external_product_assign", "cmux_assign", "blind_rotate_assign",
-           "programmable_bootstrap_f128_lwe_ciphertext", "MS_STANDARD", "MS_CENTERED", "MS_PRE_SWITCHED"]
+           "programmable_bootstrap_f128_lwe_ciphertext", "LweMultiBitBootstrapKey128", "multi_bit_limb_plan",
+           "multi_bit_blind_rotate_assign", "multi_bit_programmable_bootstrap_f128_lwe_ciphertext",
+           "MS_STANDARD", "MS_CENTERED", "MS_PRE_SWITCHED"]

@@ -1,11 +1,13 @@
 // Host check of mi::fft::decompose_l1_hi (csrc/fft64_decomp.hpp) against a plain restatement of the reference's
-// native level-1 decomposition (commons/math/decomposition/decomposer.rs:156-185 init, iter.rs:131-151 one level),
+// native level-1 decomposition (commons/math/decomposition/decomposer.rs:156-185 init, iter.rs:131-151 one level)
+// and against csrc/core_scalar.hpp's decomp_init / decomp_next, which the kernels run above base_log 31,
 // for every base_log 1..31 on the rounding corners (values around every multiple of 2^(63-B)) and random words.
 // Build: hipcc -O2 -x hip fft_decomp_check.cpp -o fft_decomp_check (host code only, no GPU needed).
 #include <stdio.h>
 #include <stdint.h>
 #include <random>
 
+#include "../../tfhe-rs-main_modified_amd/csrc/core_scalar.hpp"
 #include "../../tfhe-rs-main_modified_amd/csrc/fft64_decomp.hpp"
 
 static uint64_t init_native(uint64_t input, int base_log, int level) {
@@ -35,8 +37,10 @@ int main() {
       uint64_t st = init_native(x, B, 1);
       const int64_t want = one_level(B, st);
       const int32_t got = mi::fft::decompose_l1_hi((uint32_t)(x >> 32), B);
+      uint64_t shared_st = mi::core::decomp_init<uint64_t>(x, B, 1);
+      const int64_t shared = (int64_t)mi::core::decomp_next<uint64_t>(B, shared_st);
       ++checked;
-      if ((int64_t)got != want) {
+      if ((int64_t)got != want || shared != want) {
         if (bad++ < 10) printf("B=%d x=%016llx want %lld got %d\n", B, (unsigned long long)x, (long long)want, got);
       }
     };

@@ -1,12 +1,15 @@
-// Host check of the 128-bit packing keyswitch's digit functions (csrc/ks128_decomp.hpp: decomp_init_pre_rounded,
-// decompose_one, digit_byte, signed_bytes16) against a plain restatement of the reference's decomposition in unsigned
-// __int128 (commons/math/decomposition/decomposer.rs:25-49 closest representable, :156-185 init, iter.rs:131-151 one
-// level) and against digits computed elsewhere.
+// Host check of the 128-bit packing keyswitch's digit functions (csrc/core_scalar.hpp: the pre-rounded decomp_init and
+// decomp_next at u128, read as int64_t as the kernel does; csrc/ks128_decomp.hpp: digit_byte, signed_bytes16) against a
+// plain restatement of the reference's decomposition in unsigned __int128 (commons/math/decomposition/
+// decomposer.rs:25-49 closest representable, :156-185 init, iter.rs:131-151 one level) and against digits computed
+// elsewhere.
 // Input (stdin), one case per line: base_log level word_hi(hex) word_lo(hex) term_0 .. term_{level-1} (signed decimal,
 // least significant level first: the digits of closest_representable(word)).
 // Per case: every digit equals the restatement's and the listed one, its nd = ceil((B + 1) / 8) signed bytes recompose
 // to it, and the word's 16 signed bytes recompose to the word mod 2^128.  On top of the listed cases: every base_log
-// 1..63 at one level on the words around 0 and 2^127 and on random words.
+// 1..63 at one level on the words around 0 and 2^127 and on random words.  On every one of these words the plain form
+// (pre_rounded = false: the 128-bit bootstraps' use, read as they read it) must equal the restatement's digits of the
+// word itself too.
 // Build: hipcc -O2 -x hip ks128_decomp_check.cpp -o ks128_decomp_check (host code only, no GPU needed).
 #include <inttypes.h>
 #include <stdint.h>
@@ -51,16 +54,23 @@ static void report(const char* what, int B, int L, u128 x, int l) {
 // the digits of one word as the kernels compute them; `listed` may be null
 static void check(int B, int L, u128 x, const int64_t* listed) {
   u128 want_state = init_native(closest(x, B, L), B, L);
-  u128 state = mi::ks128::decomp_init_pre_rounded(x, B, L);
+  u128 state = mi::core::decomp_init<u128>(x, B, L, true);
   const int nd = mi::ks128::digit_bytes(B);
   if (nd != (B + 1 + 7) / 8 || nd > 8) report("digit_bytes", B, L, x, -1);
   for (int l = 0; l < L; ++l) {
     const i128 want = one_level(B, want_state);
-    const int64_t got = mi::ks128::decompose_one(B, state);
+    const int64_t got = (int64_t)(i128)mi::core::decomp_next<u128>(B, state);
     i128 from_bytes = 0;  // sum_s e_s 256^s, as the GEMM recomposes the digit
     for (int s = 0; s < nd; ++s) from_bytes += (i128)mi::ks128::digit_byte(got, s) * ((i128)1 << (8 * s));
     ++checked;
     if ((i128)got != want || (listed && got != listed[l]) || from_bytes != want) report("digit", B, L, x, l);
+  }
+  u128 want_plain = init_native(x, B, L), plain = mi::core::decomp_init<u128>(x, B, L);
+  for (int l = 0; l < L; ++l) {
+    const i128 want = one_level(B, want_plain);
+    const int64_t got = (int64_t)(uint64_t)mi::core::decomp_next<u128>(B, plain);
+    ++checked;
+    if ((i128)got != want) report("plain digit", B, L, x, l);
   }
   int8_t b[16];
   mi::ks128::signed_bytes16(x, b);

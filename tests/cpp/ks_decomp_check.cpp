@@ -1,6 +1,7 @@
-// Host check of the keyswitch digit functions (csrc/ks_decomp.hpp: decomp_init, decompose_one, signed_byte) against
-// a plain restatement of the reference's native decomposition (commons/math/decomposition/decomposer.rs:25-49 closest
-// representable, :156-185 init, iter.rs:131-151 one level) and against digits computed elsewhere.
+// Host check of the keyswitch digit functions (csrc/core_scalar.hpp: decomp_init, decomp_next at u64, read as int64_t as
+// the kernels do; csrc/ks_decomp.hpp: signed_byte) against a plain restatement of the reference's native decomposition
+// (commons/math/decomposition/decomposer.rs:25-49 closest representable, :156-185 init, iter.rs:131-151 one level) and
+// against digits computed elsewhere.
 // Input (stdin), one case per line: base_log level pre_rounded word(hex) term_0 .. term_{level-1} (signed decimal,
 // least significant level first; pre_rounded 1 = the packing keyswitch's digits of closest_representable(word)).
 // Per case: every digit equals the restatement's and the listed one, and its nd = ceil((B + 1) / 8) signed bytes, the
@@ -42,11 +43,11 @@ static long checked = 0, bad = 0;
 // the digits of one word as the kernels compute them; `listed` may be null
 static void check(int B, int L, bool pre, uint64_t x, const int64_t* listed) {
   uint64_t want_state = init_native(pre ? closest(x, B, L) : x, B, L);
-  uint64_t state = mi::ks::decomp_init(x, B, L, pre);
+  uint64_t state = mi::core::decomp_init<uint64_t>(x, B, L, pre);
   const int nd = (B + 1 + 7) / 8;
   for (int l = 0; l < L; ++l) {
     const int64_t want = one_level(B, want_state);
-    const int64_t got = mi::ks::decompose_one(B, state);
+    const int64_t got = (int64_t)mi::core::decomp_next<uint64_t>(B, state);
     uint64_t from_bytes = 0;  // sum_s e_s 256^s mod 2^64, as the GEMM's key rows shifted by 8 s recompose it
     for (int s = 0; s < nd; ++s)
       from_bytes += (uint64_t)(int64_t)mi::ks::signed_byte((uint64_t)got, s) << (8 * s);

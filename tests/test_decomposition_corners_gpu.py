@@ -7,19 +7,19 @@ oracle and, where a probe isolates the digits, with the big-integer transcriptio
 product under the bound of test_fft_gpu.test_external_product_vs_exact.
 
 Device decomposer                                                   reached by
-  keyswitch.hip ks_digits_l_kernel<1|2|4|8> (ks_decomp.hpp)          test_keyswitch_digit_probe (5,1) (6,2) (4,4) (3,8)
+  keyswitch.hip ks_digits_l_kernel<1|2|4|8> (core_scalar.hpp)        test_keyswitch_digit_probe (5,1) (6,2) (4,4) (3,8)
   keyswitch.hip ks_digits_kernel                                     test_keyswitch_digit_probe, every other shape
   ... pre_rounded (packing)                                          test_packing_keyswitch_digit_probe
   ... KS32                                                           test_ks32_digit_probe
   pbs_tw.hip generated bodies (gen_pbs_kernel.py decompose[_sol])    test_ntt_external_product_corners N = 2048 (23,1) (31,1),
                                                                      test_pbs_one_step_corners N = 2048 (23,1)
-  pbs_device.hpp decomp_init_native / closest_abs_nonnative          ... N = 2048 every other shape, N = 512 k = 4
+  core_scalar.hpp NttDigits                                          ... N = 2048 every other shape, N = 512 k = 4
     (pbs_kernels.hip, runtime level count)
   pbs_large.hip                                                      ... N = 8192
   fft64_decomp.hpp decompose_l1_hi (fft64_pbs.hip, level 1)          test_fft_external_product_corners N = 2048 (23,1) (31,1),
                                                                      test_fft_pbs_one_step_corners
-  fft64_device.hpp (fft64_pbs.hip multi-level)                       test_fft_external_product_corners N = 2048 (12,2) (8,3)
-  fft64_device.hpp (fft64_generic.hip)                               test_fft_external_product_corners N = 256
+  core_scalar.hpp (fft64_pbs.hip multi-level)                        test_fft_external_product_corners N = 2048 (12,2) (8,3)
+  core_scalar.hpp (fft64_generic.hip)                                test_fft_external_product_corners N = 256
 """
 import numpy as np
 import pytest

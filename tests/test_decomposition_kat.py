@@ -12,8 +12,10 @@ The restatements: ``decomp_corners.py_decompose`` (big integers), the C oracle's
   digits differ from the plain ones on at least one word;
 * the non-native transcription against the oracle's Solinas external product through a one-row probe, and the BNF
   probe the GPU tests use;
-* the keyswitch's device digit functions (csrc/ks_decomp.hpp), compiled for the host, on the corpus and on every
-  base_log 1..63 (tests/cpp/ks_decomp_check.cpp).
+* the kernels' own digit functions (csrc/core_scalar.hpp: decomp_init / decomp_next, NttDigits; csrc/ks_decomp.hpp:
+  signed_byte), compiled for the host: the keyswitches' on the corpus and on every base_log 1..63
+  (tests/cpp/ks_decomp_check.cpp), the NTT paths' digit stream on the corpus of the probes above
+  (tests/cpp/ntt_digits_check.cpp).
 """
 import os
 import subprocess
@@ -197,10 +199,11 @@ def test_bnf_probe_returns_the_digits(oracle, base_log, level):
                 assert np.array_equal(switched, np.array([terms[li] % M64 for terms in want[r]], dtype=np.uint64))
 
 
-# ---- the keyswitch's device digit functions, compiled for the host ----
+# ---- the kernels' own digit functions, compiled for the host ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_keyswitch_digit_functions_on_host(tmp_path):
-    """csrc/ks_decomp.hpp against tests/cpp/ks_decomp_check.cpp's restatement and against py_decompose's digits, plain
+    """csrc/core_scalar.hpp's decomp_init / decomp_next and csrc/ks_decomp.hpp's signed_byte against
+    tests/cpp/ks_decomp_check.cpp's restatement and against py_decompose's digits, plain
     and pre-rounded, on the corpus of every keyswitch shape (digits wider than 32 bits included); the check itself
     adds every base_log 1..63 at one level.  Each digit must also recompose from the signed bytes the GEMM gets."""
     exe = str(tmp_path / "ks_decomp_check")
@@ -211,6 +214,40 @@ def test_keyswitch_digit_functions_on_host(tmp_path):
         for w in D.corner_words(base_log, level):
             for pre, fn in ((0, D.py_decompose), (1, D.py_decompose_pre_rounded)):
                 lines.append(" ".join([str(base_log), str(level), str(pre), f"{w:x}"] + [str(t) for t in fn(w, base_log, level)]))
+    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout
+    assert f"{len(lines)} listed cases" in out.stdout and " 0 mismatches" in out.stdout
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_ntt_digit_streams_on_host(oracle, tmp_path):
+    """csrc/core_scalar.hpp's NttDigits<true> / NttDigits<false> (the digit stream of pbs_kernels.hip and pbs_large.hip)
+    on the corpus of the two probe tests above at D.NTT_SHAPES.  Required: the digits the oracle's one-row probe
+    returns for component 0 (Solinas: the digit polynomial itself mod p; BNF: its p -> 2^64 switch, an injective map of
+    [0, p), so the digit mod p whose switch the probe returned)."""
+    exe = str(tmp_path / "ntt_digits_check")
+    subprocess.run([HIPCC, "-O2", "-x", "hip", os.path.join(ROOT, "tests", "cpp", "ntt_digits_check.cpp"), "-o", exe],
+                   check=True, capture_output=True, timeout=300)
+    ctx = oracle.NttContext(PROBE_N)
+    lines = []
+    for base_log, level in D.NTT_SHAPES:
+        for bnf in (1, 0):
+            words = D.corner_words(base_log, level) if bnf else D.corner_words_nonnative(base_log, level, P)
+            glwe = D.corner_batch(words, (2, PROBE_N), H.rng(base_log + level), q=0 if bnf else P)
+            digits = []
+            for li in range(level):
+                ggsw = D.probe_ggsw(level, 1, PROBE_N, li, 0, 1 if bnf else ctx.plan.n_inv)
+                got = ctx.ext_product(np.zeros(2 * PROBE_N, np.uint64), ggsw.reshape(-1), glwe.reshape(-1), 1, base_log,
+                                      level, bnf=bool(bnf)).reshape(2, PROBE_N)[0]
+                if bnf:  # undo the switch: the candidates are the digits mod p of the big-integer decomposition
+                    cand = [D.py_decompose(int(x), base_log, level)[li] % P for x in glwe[0]]
+                    assert [D.bnf_switch(c, P) for c in cand] == [int(v) for v in got]
+                    got = cand
+                digits.append([int(v) for v in got])
+            for j in range(len(words)):  # coefficient j of component 0 is words[j] (corner_poly, roll 0)
+                assert int(glwe[0, j]) == words[j]
+                lines.append(" ".join([str(bnf), str(base_log), str(level), f"{words[j]:x}"] +
+                                      [str(digits[li][j]) for li in range(level)]))
     out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout
     assert f"{len(lines)} listed cases" in out.stdout and " 0 mismatches" in out.stdout

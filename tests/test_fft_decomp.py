@@ -1,6 +1,6 @@
-"""Host check of the f64-FFT PBS level-1 digit (csrc/fft64_decomp.hpp) against the reference's native
-decomposition restated in C (tests/cpp/fft_decomp_check.cpp): every base_log 1..31, rounding corners and random
-words.  No GPU: hipcc builds host code only."""
+"""Host check of the f64-FFT PBS level-1 digit (csrc/fft64_decomp.hpp) and of the shared native decomposition
+(csrc/core_scalar.hpp) against the reference's native decomposition restated in C (tests/cpp/fft_decomp_check.cpp):
+every base_log 1..31, rounding corners and random words.  No GPU: hipcc builds host code only."""
 import os
 import shutil
 import subprocess

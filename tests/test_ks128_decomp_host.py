@@ -1,8 +1,9 @@
-"""Host check of csrc/ks128_decomp.hpp (the pre-rounded SignedDecomposer<u128> and the signed-byte recodings of the
-128-bit packing keyswitch): tests/cpp/ks128_decomp_check.cpp compares them with a restatement in unsigned __int128 and
+"""Host check of the 128-bit packing keyswitch's digit functions (the pre-rounded SignedDecomposer<u128> of
+csrc/core_scalar.hpp and the signed-byte recodings of csrc/ks128_decomp.hpp): tests/cpp/ks128_decomp_check.cpp compares
+them with a restatement in unsigned __int128 (and the plain decomposition of the 128-bit bootstraps with it too) and
 with the digits pbs128_helpers.py_decompose gives for closest_representable(word), on corner_words, tie_words128 and
 random words at the six (base_log, level) pairs of the packing keyswitch tests; every digit recomposes from its nd
-signed bytes and every word from its 16.  No GPU: hipcc builds the header's host side."""
+signed bytes and every word from its 16.  No GPU: hipcc builds the headers' host side."""
 import os
 import subprocess
 

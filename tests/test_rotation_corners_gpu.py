@@ -21,7 +21,7 @@ Device copy                                                          reached by
   pbs_kernels.hip pbs_kernel<LOGN, K> (launch_pbs: block =             test_integer_paths[2048-1-12-2] T = 256,
     Shape<LOGN, K>::T = N / 8 for k <= 2, N / 4 for k >= 3),            [512-4-23-1] T = 128, [1024-2-15-2] T = 128,
     lift_switched_kernel for PRE_SWITCHED                               [4096-1-23-1] T = 512; test_lut_indexed[2048-1-12-2]
-  pbs_device.hpp centered_body_correction<T>                           test_centered_lengths, the same four shapes, W = T
+  core_device.hpp centered_body_correction<T> (pbs_kernels.hip)        test_centered_lengths, the same four shapes, W = T
   pbs_large.hip large_init_acc, large_extract (finishing pass)         every N >= 8192 case below
   pbs_large.hip large_rotdec_top<2, ., true> (split_first_pass:        test_integer_paths[8192-1-23-1], [8192-1-12-2] (MAC
     logn - 11 = 2 in one pass)                                          fused: inv_mac_supported l (k + 1) = 2, 4),
@@ -41,7 +41,7 @@ Device copy                                                          reached by
                                                                         test_fft_centered_lengths[1024-1-23-1] (corr[] pass)
   fft64_pbs.hip pbs_kernel_k1l1                                        test_fft_paths[2048-1-23-1]
   fft64_pbs.hip pbs_kernel<K, L1> (multi-level, k = 2)                 test_fft_paths[2048-1-12-2], [2048-2-12-2], [2048-2-23-1]
-  fft64_device.hpp centered_body_correction<TG>, TG = 64 (k + 1)       test_fft_centered_lengths[2048-1-23-1] W = 128,
+  core_device.hpp centered_body_correction<TG>, TG = 64 (k + 1)        test_fft_centered_lengths[2048-1-23-1] W = 128,
                                                                         [2048-2-12-2] W = 192
   fft64_generic.hip rotate / decompose pass, LUT division, lanes       test_fft_paths[256-1-23-1], [1024-1-10-2],
                                                                         [8192-1-12-2] (batch 70: four lanes)
@@ -206,7 +206,7 @@ def test_large_other_tops(engine, oracle, n, bnf):
 # (N, k, base_log, level, W): W the reduction width of the copy of the correction the shape runs
 CENTERED_SHAPES = [
     (2048, 1, 23, 1, 128),   # pbs_tw.hip centered_body_correction
-    (2048, 1, 12, 2, 256),   # pbs_device.hpp centered_body_correction<T>, T = Shape<11, 1>::T
+    (2048, 1, 12, 2, 256),   # core_device.hpp centered_body_correction<T>, T = Shape<11, 1>::T
     (512, 4, 23, 1, 128),    # T = Shape<9, 4>::T
     (1024, 2, 15, 2, 128),   # T = Shape<10, 2>::T
     (4096, 1, 23, 1, 512),   # T = Shape<12, 1>::T
@@ -316,7 +316,7 @@ def test_fft_paths(engine, n, k, base_log, level, mode):
 
 # (N, k, base_log, level, W)
 FFT_CENTERED = [
-    (2048, 1, 23, 1, 128),   # fft64_device.hpp centered_body_correction<TG>, TG = 64 (k + 1) = 128 (pbs_kernel_k1l1)
+    (2048, 1, 23, 1, 128),   # core_device.hpp centered_body_correction<TG>, TG = 64 (k + 1) = 128 (pbs_kernel_k1l1)
     (2048, 2, 12, 2, 192),   # TG = 192 (pbs_kernel<2, false>): not a power of two
     (1024, 1, 23, 1, 256),   # fft64_generic.hip: pbs_passes.hip launch_body_correction into corr[]
 ]

@@ -8,7 +8,7 @@ namespace mi {
 namespace fft {
 
 // Level-1 signed digit of a native u64 for base_log B <= 31, from the high word alone: the same value as
-// decomp_init_native + decompose_one_level in fft64_pbs.hip (decomposer.rs:156-185, iter.rs:131-151).
+// core_scalar.hpp's decomp_init + decomp_next at one level (decomposer.rs:156-185, iter.rs:131-151).
 // With t = the top B + 1 bits (x >> (63 - B)), the reference's digit is the B-bit value ((t + 1) >> 1) mod 2^B
 // read as signed (two's complement), except for the one unbalanced tie t = 2^B (binary 10...0), whose digit is
 // +2^(B-1) instead of -2^(B-1) (its rounding bit is 0, so need_balance stays 0).  With s = 31 - B:

@@ -1,10 +1,12 @@
 // fft64_device.hpp — device helpers shared by the f64-FFT engines: the N = 2048 one-wave engine (fft64_pbs.hip) and
 // the shape-generic engine (fft64_generic.hip).  Complex f64 arithmetic (FMA-contracted as the reference's pulp
-// kernels' mul_add), the torus conversions of fft_impl/fft64/math/fft/mod.rs, the native decomposition and the
-// modulus switch of the blind rotation.
+// kernels' mul_add) and the torus conversions of fft_impl/fft64/math/fft/mod.rs; the native decomposition, the modulus
+// switch and the monomial rules of the blind rotation are core_scalar.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "core_device.hpp"
 
 namespace mi {
 namespace fft {
@@ -83,67 +85,18 @@ __device__ __forceinline__ void add_torus(u64& acc, double t) {
   acc = ((u64)nhi << 32) | nlo;
 }
 
-// ---- decomposition (commons/math/decomposition/decomposer.rs:156-185, iter.rs:131-151) ------------
-__device__ __forceinline__ u64 decomp_init_native(u64 input, int base_log, int level) {
-  const unsigned rep = base_log * level, non_rep = 64u - rep;
-  u64 res = input >> (non_rep - 1);
-  const u64 rounding_bit = res & 1u;
-  res += 1;
-  res >>= 1;
-  res &= (~0ull) >> (64u - rep);
-  const u64 need_balance = (((res - 1) | (rounding_bit << (rep - 1))) & res) >> (rep - 1);
-  return res - (need_balance << rep);
+// ---- the native decomposition, the modulus switch and the centered correction: core_scalar.hpp's ----
+using core::decomp_init;
+using core::decomp_next;
+__device__ __forceinline__ u64 decomp_init_native(u64 x, int base_log, int level) {
+  return core::decomp_init<u64>(x, base_log, level);
 }
 __device__ __forceinline__ u64 decompose_one_level(int base_log, u64& state) {
-  const u64 mask = (1ull << base_log) - 1;
-  const u64 res = state & mask;
-  state = (u64)((int64_t)state >> base_log);
-  const u64 carry = (((res - 1) | state) & res) >> (base_log - 1);
-  state += carry;
-  return res - (carry << base_log);
+  return core::decomp_next<u64>(base_log, state);
 }
-
-// fft_impl/common.rs:10-23
-__device__ __forceinline__ u64 modulus_switch(u64 input, unsigned log_modulus) {
-  return (input + (1ull << (64u - log_modulus - 1u))) >> (64u - log_modulus);
-}
-
-// algorithms/modulus_switch.rs:60-104 centered_binary_ms_body_correction_to_add, reduced over the TG threads of
-// one ciphertext (gt = index within them; sh = 2 TG u64 of that ciphertext's LDS).  Every thread of the
-// workgroup calls it (barriers).
-template <int TG>
-__device__ u64 centered_body_correction(const u64* __restrict__ lwe, uint32_t n_lwe, unsigned log_mod, int gt,
-                                        u64* sh) {
-  u64 sum_half = 0;
-  int64_t sum_hed = 0;
-  for (uint32_t i = gt; i < n_lwe; i += TG) {
-    const u64 a = lwe[i];
-    const int64_t err = (int64_t)((modulus_switch(a, log_mod) << (64u - log_mod)) - a);
-    const int64_t half = err / 2;
-    sum_half += (u64)half;
-    sum_hed += 2 * half - err;
-  }
-  sh[gt] = sum_half;
-  sh[TG + gt] = (u64)sum_hed;
-  __syncthreads();
-  // TG = 64 (k + 1) is no power of two at k = 2 (192 -> ... -> 3 -> 2 -> 1): the upper part of the `live` entries
-  // folds onto the lower one, and an odd count keeps its middle entry for the next round
-  for (int live = TG; live > 1;) {
-    const int s = (live + 1) / 2;
-    if (gt + s < live) {
-      sh[gt] += sh[gt + s];
-      sh[TG + gt] = (u64)((int64_t)sh[TG + gt] + (int64_t)sh[TG + gt + s]);
-    }
-    __syncthreads();
-    live = s;
-  }
-  const u64 total_half = sh[0];
-  const int64_t total_hed = (int64_t)sh[TG];
-  __syncthreads();
-  const u64 sum_halving = (u64)(total_hed / 2);
-  const u64 half_case = 1ull << (64u - log_mod - 1u);
-  return total_half - sum_halving - half_case;
-}
+using core::centered_body_correction;
+using core::Monomial;
+using core::modulus_switch;
 
 }  // namespace fft
 }  // namespace mi

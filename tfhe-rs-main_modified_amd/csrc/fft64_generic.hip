@@ -133,8 +133,8 @@ struct TorusSrc {
 
 // digit li of the signed decomposition (least significant level first, as the iterator yields them)
 __device__ __forceinline__ u64 digit(u64 x, int base_log, int level, int li) {
-  u64 st = decomp_init_native(x, base_log, level), d = 0;
-  for (int i = 0; i <= li; ++i) d = decompose_one_level(base_log, st);
+  u64 st = decomp_init<u64>(x, base_log, level), d = 0;
+  for (int i = 0; i <= li; ++i) d = decomp_next<u64>(base_log, st);
   return d;
 }
 
@@ -168,15 +168,14 @@ struct RotDigitSrc {
     const uint64_t b = p / ((uint64_t)kp1 * level);
     const uint32_t nn = 1u << logn, m = nn >> 1;
     const u64 a_raw = lwe[b * (n_lwe + 1) + step];
-    const uint32_t a = (uint32_t)(ms_mode == 2 ? (a_raw & (2 * nn - 1)) : modulus_switch(a_raw, logn + 1));
-    const uint32_t full = (a >> logn) & 1u, rem = a & (nn - 1);
+    const Monomial xa(ms_mode == 2 ? a_raw : modulus_switch(a_raw, logn + 1), logn);
     const u64* ap = acc + ((b * kp1 + c) << logn);
     u64 ct[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const uint32_t e = n + (h ? m : 0u);
-      u64 v = ap[(e - rem) & (nn - 1)];  // new[e] = old[(e - rem) mod N], negated for e < rem (and when full)
-      if (full ^ (e < rem ? 1u : 0u)) v = (u64)0 - v;
+      u64 v = ap[xa.mul_src(e, nn)];
+      if (xa.mul_neg(e)) v = (u64)0 - v;
       ct[h] = digit(v - ap[e], base_log, (int)level, (int)li);
     }
     return cmul(cplx{s64_to_f64(ct[0]), s64_to_f64(ct[1])}, tw[n]);
@@ -446,15 +445,14 @@ __global__ __launch_bounds__(256) void init_acc_kernel(u64* __restrict__ acc, Pb
       continue;
     }
     const u64 bv = lwe[b * (n_lwe + 1) + n_lwe];
-    const u64 body = ms_mode == 2 ? (bv & (2 * nn - 1)) : modulus_switch(bv + (corr ? corr[b] : 0), logn + 1);
-    const uint32_t full = (uint32_t)(body >> logn) & 1u, rem = (uint32_t)body & (nn - 1);
-    u64 v = lut[((uint64_t)c << logn) + ((m + rem) & (nn - 1))];
-    if (full ^ (m >= nn - rem ? 1u : 0u)) v = (u64)0 - v;
+    const Monomial xb(ms_mode == 2 ? bv : modulus_switch(bv + (corr ? corr[b] : 0), logn + 1), logn);
+    u64 v = lut[((uint64_t)c << logn) + xb.div_src(m, nn)];
+    if (xb.div_neg(m, nn)) v = (u64)0 - v;
     acc[i] = v;
   }
 }
 
-// extract_lwe_sample_from_glwe_ciphertext, nth = 0: out[c N] = A_c[0], out[c N + j] = -A_c[N - j], out[k N] = B[0];
+// extract_lwe_sample_from_glwe_ciphertext, nth = 0 (Monomial::extract_*) per mask polynomial, out[k N] = B[0];
 // items whose LUT index is out of range (io.lut_idx) are not written
 __global__ __launch_bounds__(256) void extract_kernel(u64* __restrict__ out, const u64* __restrict__ acc,
                                                       uint32_t batch, uint32_t logn, uint32_t k, PbsIo io, uint64_t b0) {
@@ -464,8 +462,8 @@ __global__ __launch_bounds__(256) void extract_kernel(u64* __restrict__ out, con
     const uint64_t b = i / per_out, o = i % per_out;
     if (io.lut_idx && !io.lut_for(b0 + b, per)) continue;
     const uint32_t c = (uint32_t)(o >> logn), j = (uint32_t)o & (nn - 1);
-    const u64 v = acc[b * per + ((uint64_t)c << logn) + (j ? nn - j : 0u)];
-    out[i] = (c == k || j == 0) ? v : (u64)0 - v;
+    const u64 v = acc[b * per + ((uint64_t)c << logn) + Monomial::extract_src(j, nn)];  // the body (c = k) has j = 0
+    out[i] = Monomial::extract_neg(j) ? (u64)0 - v : v;
   }
 }
 

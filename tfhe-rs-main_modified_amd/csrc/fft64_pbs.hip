@@ -317,7 +317,7 @@ __device__ __forceinline__ void pbs_body(u64* __restrict__ lwe_out, const u64* _
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // polynomial_wrapping_monic_monomial_mul_and_subtract: ct1[e] = s_e acc[(e - rem) mod N] - acc[e], s_e = -1 iff
-    // full ^ (e < rem).  With m = s_e < 0 ? ~0 : 0:  s_e v - acc = (v ^ m) - (acc + m).
+    // Monomial::mul_neg(e) (core_scalar.hpp; the source is its mul_src, restated here on byte addresses).  With m = s_e < 0 ? ~0 : 0:  s_e v - acc = (v ^ m) - (acc + m).
     // Source of e = lane + 64 r: (e - rem) mod N at byte rot + 512 r (no wrap: e >= rem) or that minus 16 KiB.
     // Lanes >= rem never wrap; below rem, e < rem holds exactly for the wrapped sources, which are the
     // in-range ones — so one per-lane base (A or A - 16 KiB) selected by the same compare as the sign, and the

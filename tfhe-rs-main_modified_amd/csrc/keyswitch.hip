@@ -46,7 +46,8 @@ namespace ks {
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 using u64 = uint64_t;
 
-// decomp_init, decompose_one, signed_byte: ks_decomp.hpp (host-callable, checked by tests/cpp/ks_decomp_check.cpp)
+// the digits: core_scalar.hpp's decomp_init / decomp_next read as signed (|digit| <= 2^(B-1) with base_log up to 63 at
+// one level needs all 64 bits); signed_byte: ks_decomp.hpp (both checked on the host by tests/cpp/ks_decomp_check.cpp)
 
 struct Shape {
   uint32_t in_dim, out_size, level, base_log, nd, K, KB, CT;
@@ -145,8 +146,8 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     u64 state = 0;
     int64_t d = 0;
     if (live && k0 < s.K) {  // the state after terms 0..li of coefficient i
-      state = decomp_init(x[i], bl, lv, pre);
-      for (uint32_t u = 0; u <= li; ++u) d = decompose_one(bl, state);
+      state = core::decomp_init<u64>(x[i], bl, lv, pre);
+      for (uint32_t u = 0; u <= li; ++u) d = (int64_t)core::decomp_next<u64>(bl, state);
     }
     for (int j = 0; j < 16; ++j) {
       const uint32_t k = k0 + j;
@@ -157,9 +158,9 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
         if (++li == s.level) {  // next mask coefficient
           li = 0;
           ++i;
-          if (on) state = decomp_init(x[i], bl, lv, pre);
+          if (on) state = core::decomp_init<u64>(x[i], bl, lv, pre);
         }
-        if (on) d = decompose_one(bl, state);
+        if (on) d = (int64_t)core::decomp_next<u64>(bl, state);
       }
     }
     afrag[idx] = pack16(b);
@@ -195,10 +196,10 @@ __global__ __launch_bounds__(256) void ks_digits_l_kernel(uint4* __restrict__ af
     const uint32_t kbi = cw / CPB, c = cw % CPB;
     const uint32_t row = mg * GM * 16 + R, i = kb0 * CPB + cw;
     const u64 x = (row < batch && i < s.in_dim) ? lwe_in[(uint64_t)row * (s.in_dim + 1) + i] : 0;
-    u64 state = decomp_init(x, bl, LEVEL, s.pre_rounded != 0);  // 0 decomposes to 0 at every level (padding rows / columns)
+    u64 state = core::decomp_init<u64>(x, bl, LEVEL, s.pre_rounded != 0);  // 0 decomposes to 0 at every level (padding rows / columns)
     W w = 0;
 #pragma unroll
-    for (int l = 0; l < LEVEL; ++l) w |= (W)(uint8_t)(int8_t)decompose_one(bl, state) << (8 * l);
+    for (int l = 0; l < LEVEL; ++l) w |= (W)(uint8_t)(int8_t)(int64_t)core::decomp_next<u64>(bl, state) << (8 * l);
     const uint32_t kk = LEVEL * c, lane = (kk >> 4) * 16 + (R & 15);
     *reinterpret_cast<W*>(bytes + ((kbi * GM + (R >> 4)) * 64 + lane) * 16 + (kk & 15)) = w;
   }
@@ -397,41 +398,31 @@ __global__ __launch_bounds__(64 * NW, 1) void ks_gemm_kernel(void* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(256) void lwe_ms_kernel(u64* __restrict__ out, const T* __restrict__ in, uint32_t dim,
                                                      uint32_t batch, uint32_t log_mod, int centered) {
-  using S = typename std::conditional<sizeof(T) == 4, int32_t, int64_t>::type;
-  constexpr uint32_t BITS = 8 * sizeof(T);
   const uint32_t lane = threadIdx.x & 63, item = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (item >= batch) return;
   const T* x = in + (uint64_t)item * (dim + 1);
   u64* y = out + (uint64_t)item * (dim + 1);
-  T sum_half = 0;
-  int32_t sum_hed = 0;
+  core::CenteredSums<T, int32_t> sums;
   for (uint32_t i = lane; i < dim; i += 64) {
-    const T a = x[i], sw = ms_word<T>(a, log_mod);
-    y[i] = sw;
-    if (centered) {
-      const T round = log_mod >= BITS ? sw : (T)(sw << (BITS - log_mod));
-      const S err = (S)(T)(round - a), half = err / 2;  // signed division truncates toward zero, as Rust's
-      sum_half += (T)half;
-      sum_hed += (int32_t)(2 * half - err);
-    }
+    const T a = x[i];
+    y[i] = ms_word<T>(a, log_mod);
+    if (centered) sums.add(a, log_mod);
   }
   if (centered) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
+      core::CenteredSums<T, int32_t> other;
       if constexpr (sizeof(T) == 4) {
-        sum_half += (T)__shfl_xor((int)sum_half, off, 64);
+        other.half = (T)__shfl_xor((int)sums.half, off, 64);
       } else {
-        sum_half += (T)__shfl_xor((long long)sum_half, off, 64);
+        other.half = (T)__shfl_xor((long long)sums.half, off, 64);
       }
-      sum_hed += __shfl_xor(sum_hed, off, 64);
+      other.hed = __shfl_xor(sums.hed, off, 64);
+      sums.merge(other);
     }
   }
   if (lane == 0) {
-    T corr = 0;
-    if (centered) {
-      const T half_case = (T)1 << (BITS - log_mod - 1u);
-      corr = (T)(sum_half - (T)(S)(sum_hed / 2)) - half_case;
-    }
+    const T corr = centered ? sums.correction(log_mod) : (T)0;
     y[dim] = ms_word<T>((T)(x[dim] + corr), log_mod);
   }
 }

@@ -117,8 +117,8 @@ __global__ __launch_bounds__(256) void pks128_digits_kernel(uint4* __restrict__ 
     uint32_t i = k0 / s.level, li = k0 - i * s.level;
     u128 state = 0;
     if (live && k0 < s.K) {  // the state after terms 0 .. li - 1 of coefficient i
-      state = decomp_init_pre_rounded(x[i], bl, lv);
-      for (uint32_t u = 0; u < li; ++u) (void)decompose_one(bl, state);
+      state = core::decomp_init<u128>(x[i], bl, lv, true);
+      for (uint32_t u = 0; u < li; ++u) (void)core::decomp_next<u128>(bl, state);
     }
     int64_t d[16];
 #pragma unroll
@@ -126,11 +126,11 @@ __global__ __launch_bounds__(256) void pks128_digits_kernel(uint4* __restrict__ 
       const uint32_t k = k0 + j;
       d[j] = 0;
       if (live && k < s.K) {
-        d[j] = decompose_one(bl, state);
+        d[j] = (int64_t)(i128)core::decomp_next<u128>(bl, state);
         if (++li == s.level) {  // next mask coefficient
           li = 0;
           ++i;
-          if (k + 1 < s.K) state = decomp_init_pre_rounded(x[i], bl, lv);
+          if (k + 1 < s.K) state = core::decomp_init<u128>(x[i], bl, lv, true);
         }
       }
     }

@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void glwe_decompose(u64* __restrict__ digits, 
   }
 }
 
-// acc[b] = src / X^ms(body) (polynomial_wrapping_monic_monomial_div_assign_split, bootstrap.rs:82-91): new[m] =
-// old[(m + rem) % N], negated for m >= N - rem; src = the shared LUT (src_stride 0) or the item's own accumulator
+// acc[b] = src / X^ms(body) (polynomial_wrapping_monic_monomial_div_assign_split, bootstrap.rs:82-91); src =
+// the shared LUT (src_stride 0) or the item's own accumulator
 __global__ __launch_bounds__(256) void init_acc(u64* __restrict__ acc, const u64* __restrict__ src, uint64_t src_stride,
                                                 const u64* __restrict__ lwe_in, const u64* __restrict__ corr,
                                                 uint32_t n_lwe, int pre, uint32_t batch, Shape sh) {
@@ -83,10 +83,9 @@ __global__ __launch_bounds__(256) void init_acc(u64* __restrict__ acc, const u64
     const uint64_t b = i / per, ce = i % per;
     const uint32_t c = (uint32_t)(ce >> sh.logn), m = (uint32_t)(ce & (sh.n - 1));
     const u64 raw = lwe_in[b * (n_lwe + 1) + n_lwe] + (corr ? corr[b] : 0);
-    const uint32_t body = switched(raw, sh.logn + 1, pre);
-    const uint32_t full = (body >> sh.logn) & 1u, rem = body & (sh.n - 1);
-    u128 v = ld128(src, b * src_stride + (uint64_t)c * sh.n + ((m + rem) & (sh.n - 1)));
-    if (full ^ (uint32_t)(m >= sh.n - rem)) v = (u128)0 - v;
+    const Monomial xb(switched(raw, sh.logn + 1, pre), sh.logn);
+    u128 v = ld128(src, b * src_stride + (uint64_t)c * sh.n + xb.div_src(m, sh.n));
+    if (xb.div_neg(m, sh.n)) v = (u128)0 - v;
     st128(acc, i, v);
   }
 }
@@ -100,11 +99,10 @@ __global__ __launch_bounds__(256) void rotate_decompose(u64* __restrict__ digits
   for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     const uint32_t e = (uint32_t)(ce & (sh.n - 1));
-    const uint32_t a = switched(lwe_in[b * (n_lwe + 1) + step], sh.logn + 1, pre);
-    const uint32_t full = (a >> sh.logn) & 1u, rem = a & (sh.n - 1);
+    const Monomial xa(switched(lwe_in[b * (n_lwe + 1) + step], sh.logn + 1, pre), sh.logn);
     const uint64_t base = i - e;  // the polynomial's first coefficient
-    u128 v = ld128(acc, base + ((e - rem) & (sh.n - 1)));  // X^a acc: new[e] = old[(e - rem) % N], negated for e < rem
-    if (full ^ (uint32_t)(e < rem)) v = (u128)0 - v;
+    u128 v = ld128(acc, base + xa.mul_src(e, sh.n));  // X^a acc
+    if (xa.mul_neg(e)) v = (u128)0 - v;
     decompose_store(v - ld128(acc, i), digits + b * sh.level * per + ce, per, sh.base_log, (int)sh.level);
   }
 }
@@ -175,16 +173,15 @@ __global__ __launch_bounds__(256) void recombine(u64* __restrict__ out, const u6
   }
 }
 
-// sample extraction of coefficient 0 (glwe_sample_extraction.rs:89-160): out[c N] = A_c[0], out[c N + j] = -A_c[N - j],
-// out[k N] = B[0]
+// sample extraction of coefficient 0 (Monomial::extract_*) per mask polynomial, out[k N] = B[0]
 __global__ __launch_bounds__(256) void extract(u64* __restrict__ lwe_out, const u64* __restrict__ acc, uint32_t batch,
                                                Shape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, per_out = (uint64_t)sh.k * sh.n + 1, total = per_out * batch;
   for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per_out, o = i % per_out;
     const uint32_t c = (uint32_t)(o >> sh.logn), j = (uint32_t)(o & (sh.n - 1));  // o = k N gives c = k, j = 0
-    const u128 v = ld128(acc, b * per + (uint64_t)c * sh.n + (j == 0 ? 0 : sh.n - j));
-    st128(lwe_out, i, j == 0 ? v : (u128)0 - v);
+    const u128 v = ld128(acc, b * per + (uint64_t)c * sh.n + Monomial::extract_src(j, sh.n));
+    st128(lwe_out, i, Monomial::extract_neg(j) ? (u128)0 - v : v);
   }
 }
 

@@ -1,5 +1,5 @@
 // pbs128_device.hpp — what the two 128-bit bootstraps share (pbs128.hip: the classic one; pbs128_multi_bit.hip: the
-// multi-bit one): the kernel-side shape, the u128 accesses, SignedDecomposer<u128>, the sums of the mac, the routing of
+// multi-bit one): the kernel-side shape, the u128 accesses, the digits of a u128 as residues, the sums of the mac, the routing of
 // the plan's transform, the chunk plan, and the launchers of pbs128.hip's passes that the multi-bit step reuses.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 namespace mi {
 namespace pbs128 {
 
+using pbs::Monomial;
 using pbs::P;
 typedef unsigned __int128 u128;
 typedef __int128 i128;
@@ -36,35 +37,15 @@ __device__ __forceinline__ void st128(u64* p, uint64_t i, u128 v) {
   *reinterpret_cast<u64x2*>(p + 2 * i) = w;
 }
 
-// SignedDecomposer<u128>::init_decomposer_state (decomposer.rs:156-185); rep = base_log * level in [1, 127], so the
-// shifts and the balancing bit span both words
-__device__ __forceinline__ u128 decomp_init(u128 input, unsigned rep) {
-  u128 res = input >> (128u - rep - 1u);
-  const u128 rounding_bit = res & 1u;
-  res += 1;
-  res >>= 1;
-  res &= ~(u128)0 >> (128u - rep);
-  const u128 need_balance = (((res - 1) | (rounding_bit << (rep - 1))) & res) >> (rep - 1);
-  return res - (need_balance << rep);
-}
-
-// decompose_one_level (iter.rs:131-151) at Scalar = u128 (what collect_next_term_split_scalar, ggsw.rs:517-567, computes
-// on split words); the digit lies in [-2^(B-1), 2^(B-1)] and B <= 58 wherever a limb plan exists, so it fits an i64
-__device__ __forceinline__ int64_t decomp_next(int base_log, u128& state) {
-  const u128 mask = ((u128)1 << base_log) - 1;
-  const u128 res = state & mask;
-  state = (u128)((i128)state >> base_log);
-  const u128 carry = (((res - 1) | state) & res) >> (base_log - 1);
-  state += carry;
-  return (int64_t)(u64)(res - (carry << base_log));
-}
-
 // the `level` digits of x as canonical residues, least significant level first: dst[li * level_stride]
 __device__ __forceinline__ void decompose_store(u128 x, u64* __restrict__ dst, uint64_t level_stride, int base_log,
                                                 int level) {
-  u128 state = decomp_init(x, (unsigned)(base_log * level));
+  // SignedDecomposer<u128> (what collect_next_term_split_scalar, ggsw.rs:517-567, computes on split words); rep =
+  // base_log * level in [1, 127]; a digit lies in [-2^(B-1), 2^(B-1)] and B <= 58 wherever a limb plan exists, so it
+  // fits an i64
+  u128 state = core::decomp_init<u128>(x, base_log, level);
   for (int li = 0; li < level; ++li) {
-    const int64_t d = decomp_next(base_log, state);
+    const int64_t d = (int64_t)(u64)core::decomp_next<u128>(base_log, state);
     dst[(uint64_t)li * level_stride] = d < 0 ? P + (u64)d : (u64)d;
   }
 }

@@ -77,30 +77,13 @@ __device__ __forceinline__ void ext_product_regs(const u64 (&ct1)[K + 1][Shape<L
   constexpr int E = S::E, N = S::N;
   const Goldilocks gl;
   if constexpr (L1) level = 1;
-  // digit li of every coefficient: decomposer.rs:156-185 + iter.rs:131-151 (BNF) / iter.rs:623-745 (Solinas), mapped
-  // into [0, p) as ntt64.rs:231-238; the state arrays exist only for the runtime-level form
-  u64 state[L1 ? 1 : K + 1][L1 ? 1 : E];
-  bool sign[L1 ? 1 : K + 1][L1 ? 1 : E];
-  auto init = [&](u64 v, u64& st, bool& sg) {
-    if (BNF) {
-      st = decomp_init_native(v, base_log, level);
-      sg = false;
-    } else {
-      const unsigned shift = 64u - (unsigned)(base_log * level);
-      sg = v >= P / 2 + 1;  // div_ceil(2)
-      st = closest_abs_nonnative(sg ? P - v : v, base_log, level) >> shift;
-    }
-  };
-  auto digit = [&](u64& st, bool sg) -> u64 {
-    u64 term = decompose_one_level(base_log, st);
-    if (!BNF && sg) term = (u64)0 - term;  // iter.rs:722-731
-    return ((int64_t)term < 0) ? term + P : term;  // ntt64.rs:231-238 / iter.rs:724-730
-  };
+  // digit li of every coefficient (NttDigits); the state array exists only for the runtime-level form
+  NttDigits<BNF> digits[L1 ? 1 : K + 1][L1 ? 1 : E];
   if constexpr (!L1) {
 #pragma unroll
     for (int c = 0; c <= K; ++c)
 #pragma unroll
-      for (int r = 0; r < E; ++r) init(ct1[c][r], state[c][r], sign[c][r]);
+      for (int r = 0; r < E; ++r) digits[c][r].init(ct1[c][r], base_log, level);
   }
 #pragma unroll
   for (int c = 0; c <= K; ++c)
@@ -115,12 +98,11 @@ __device__ __forceinline__ void ext_product_regs(const u64 (&ct1)[K + 1][Shape<L
 #pragma unroll
       for (int r = 0; r < E; ++r) {
         if constexpr (L1) {
-          u64 st;
-          bool sg;
-          init(ct1[c][r], st, sg);
-          x[c][r] = digit(st, sg);
+          NttDigits<BNF> d;
+          d.init(ct1[c][r], base_log, level);
+          x[c][r] = d.next(base_log);
         } else {
-          x[c][r] = digit(state[c][r], sign[c][r]);
+          x[c][r] = digits[c][r].next(base_log);
         }
       }
     ntt_regs<G, true, K + 1, Goldilocks, true>(x, t, sh, tw, gl);  // lazy: the MAC below reduces its sums anyway
@@ -241,8 +223,7 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
     for (int r = 0; r < E; ++r) acc[c][r] = lut[c * N + elem<G>(t, r, S::LO_COL)];
 
   if (!BNF) {  // ntt64_pbs.rs:237-249: rotate the LUT by -ms(b) first (custom modulus)
-    const u64 body = ms_non_native(lwe[n_lwe], log_mod);
-    const int full = (int)(body / N) & 1, rem = (int)(body % N);
+    const Monomial xb(ms_non_native(lwe[n_lwe], log_mod), LOGN);
 #pragma unroll
     for (int c = 0; c <= K; ++c)
 #pragma unroll
@@ -252,9 +233,9 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
     for (int c = 0; c <= K; ++c)
 #pragma unroll
       for (int r = 0; r < E; ++r) {
-        const int m = elem<G>(t, r, S::LO_COL);  // div_assign: new[m] = old[(m + rem) % N], neg for m >= N - rem
-        u64 v = sh[c * N + ((m + rem) & (N - 1))];
-        if (full ^ (m >= N - rem)) v = neg_custom(v);
+        const int m = elem<G>(t, r, S::LO_COL);
+        u64 v = sh[c * N + xb.div_src(m, N)];
+        if (xb.div_neg(m, N)) v = neg_custom(v);
         acc[c][r] = v;
       }
     __syncthreads();
@@ -270,7 +251,7 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
       if (a_raw == 0) continue;  // ntt64_pbs.rs:257
       a = ms_non_native(a_raw, log_mod);
     }
-    const int full = (int)(a / N) & 1, rem = (int)(a % N);
+    const Monomial xa(a, LOGN);
     // ct1 = acc * X^a (polynomial_wrapping_monic_monomial_mul_assign[_custom_mod]) ; ct1 -= acc
 #pragma unroll
     for (int c = 0; c <= K; ++c)
@@ -282,9 +263,9 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
     for (int c = 0; c <= K; ++c)
 #pragma unroll
       for (int r = 0; r < E; ++r) {
-        const int e = elem<G>(t, r, S::LO_COL);  // mul_assign: new[e] = old[(e - rem) % N], neg for e < rem
-        u64 v = sh[c * N + ((e - rem) & (N - 1))];
-        if (full ^ (e < rem)) v = neg_q<BNF>(v);
+        const int e = elem<G>(t, r, S::LO_COL);
+        u64 v = sh[c * N + xa.mul_src(e, N)];
+        if (xa.mul_neg(e)) v = neg_q<BNF>(v);
         ct1[c][r] = BNF ? v - acc[c][r] : sub_custom(v, acc[c][r]);  // cmux: ct1 - ct0
       }
     __syncthreads();
@@ -301,12 +282,8 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
 #pragma unroll
     for (int r = 0; r < E; ++r) sh[c * N + elem<G>(t, r, S::LO_COL)] = acc[c][r];
   __syncthreads();
-  int full = 0, rem = 0;
-  if (BNF) {
-    const u64 body = modulus_switch(lwe[n_lwe] + body_corr, log_mod);
-    full = (int)(body / N) & 1;
-    rem = (int)(body % N);
-  }
+  Monomial xb;  // Solinas: rotated before the loop
+  if (BNF) xb = Monomial(modulus_switch(lwe[n_lwe] + body_corr, log_mod), LOGN);
   if (io.glwe_out) {  // blind_rotate_ntt64[_bnf]_assign: the rotated GLWE itself
     u64* g = io.glwe_out + (size_t)b * (K + 1) * N;
 #pragma unroll
@@ -314,28 +291,28 @@ void pbs_kernel(u64* __restrict__ lwe_out, const u64* __restrict__ lwe_in,
 #pragma unroll
       for (int r = 0; r < E; ++r) {
         const int m = elem<G>(t, r, S::LO_COL);
-        u64 v = sh[c * N + ((m + rem) & (N - 1))];
-        if (full ^ (m >= N - rem)) v = neg_q<BNF>(v);
+        u64 v = sh[c * N + xb.div_src(m, N)];
+        if (xb.div_neg(m, N)) v = neg_q<BNF>(v);
         g[c * N + m] = v;
       }
     return;
   }
-  // rotated[c][m] = sign * acc[c][(m + rem) % N]; glwe_sample_extraction.rs:89-160: mask polynomial c
-  // gives out[c N + 0] = A_c[0], out[c N + j] = -A_c[N - j]; the body coefficient 0 gives out[K N]
+  // sample extraction (Monomial::extract_*) of the rotated accumulator: mask polynomial c gives out[c N ..], the body
+  // coefficient 0 gives out[K N]
   u64* out = lwe_out + (size_t)b * (K * N + 1);
 #pragma unroll
   for (int c = 0; c < K; ++c)
 #pragma unroll
     for (int r = 0; r < E; ++r) {
       const int j = elem<G>(t, r, S::LO_COL);
-      const int m = (j == 0) ? 0 : N - j;
-      u64 v = sh[c * N + ((m + rem) & (N - 1))];
-      if (full ^ (m >= N - rem)) v = neg_q<BNF>(v);
-      out[c * N + j] = (j == 0) ? v : neg_q<BNF>(v);
+      const int m = Monomial::extract_src(j, N);
+      u64 v = sh[c * N + xb.div_src(m, N)];
+      if (xb.div_neg(m, N)) v = neg_q<BNF>(v);
+      out[c * N + j] = Monomial::extract_neg(j) ? neg_q<BNF>(v) : v;
     }
   if (t == 0) {
-    u64 v = sh[K * N + (rem & (N - 1))];
-    if (full ^ (0 >= N - rem)) v = neg_q<BNF>(v);
+    u64 v = sh[K * N + xb.div_src(0, N)];
+    if (xb.div_neg(0, N)) v = neg_q<BNF>(v);
     out[K * N] = v;
   }
 }

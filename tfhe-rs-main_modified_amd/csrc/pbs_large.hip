@@ -43,26 +43,23 @@ struct LargeShape {
   int base_log;
 };
 
-// signed decomposition of one GLWE coefficient into `level` digits mod p, least significant level first (the
-// order the reference's iterator yields them and the GGSW stores its blocks): BNF = decomposer.rs:156-185 +
-// iter.rs:131-151 (digits mapped into [0, p) as ntt64.rs:231-238); Solinas = iter.rs:623-745 (sign-magnitude)
+// the `level` digits of one GLWE coefficient (NttDigits), least significant level first: the order the reference's
+// iterator yields them and the GGSW stores its blocks
 template <bool BNF>
 __device__ __forceinline__ void decompose_store(u64 x, u64* __restrict__ dst, uint64_t level_stride, int base_log,
                                                 int level) {
-  u64 state;
-  bool sign = false;
-  if (BNF) {
-    state = decomp_init_native(x, base_log, level);
-  } else {
-    const unsigned shift = 64u - (unsigned)(base_log * level);
-    sign = x >= P / 2 + 1;
-    state = closest_abs_nonnative(sign ? P - x : x, base_log, level) >> shift;
-  }
-  for (int li = 0; li < level; ++li) {
-    u64 term = decompose_one_level(base_log, state);
-    if (!BNF && sign) term = (u64)0 - term;
-    dst[(uint64_t)li * level_stride] = ((int64_t)term < 0) ? term + P : term;
-  }
+  NttDigits<BNF> d;
+  d.init(x, base_log, level);
+  for (int li = 0; li < level; ++li) dst[(uint64_t)li * level_stride] = d.next(base_log);
+}
+
+// X^a of one mask element: its switch to [0, 2N]; the Solinas form skips a zero element (ntt64_pbs.rs:257), as X^0 does
+template <bool BNF>
+__device__ __forceinline__ Monomial mask_monomial(u64 a_raw, uint32_t logn) {
+  u64 a = 0;
+  if (BNF) a = modulus_switch(a_raw, logn + 1);
+  else if (a_raw != 0) a = ms_non_native(a_raw, logn + 1);
+  return Monomial(a, logn);
 }
 
 // acc[b] = the item's LUT (BNF), or the LUT rotated by -ms(body) (Solinas, ntt64_pbs.rs:237-249); item b of the chunk
@@ -81,10 +78,9 @@ __global__ __launch_bounds__(256) void large_init_acc(u64* __restrict__ acc, Pbs
     } else if (BNF) {
       acc[i] = lut[ce];
     } else {
-      const u64 body = ms_non_native(lwe_in[b * (n_lwe + 1) + n_lwe], sh.logn + 1);
-      const uint32_t full = (uint32_t)(body >> sh.logn) & 1u, rem = (uint32_t)(body & (sh.n - 1));
-      u64 v = lut[(uint64_t)c * sh.n + ((m + rem) & (sh.n - 1))];  // div_assign by X^body
-      if (full ^ (m >= sh.n - rem)) v = neg_custom(v);
+      const Monomial xb(ms_non_native(lwe_in[b * (n_lwe + 1) + n_lwe], sh.logn + 1), sh.logn);
+      u64 v = lut[(uint64_t)c * sh.n + xb.div_src(m, sh.n)];  // div_assign by X^body
+      if (xb.div_neg(m, sh.n)) v = neg_custom(v);
       acc[i] = v;
     }
   }
@@ -97,18 +93,13 @@ __global__ __launch_bounds__(256) void large_rotate_decompose(u64* __restrict__ 
                                                               const u64* __restrict__ lwe_in, uint32_t n_lwe,
                                                               uint32_t step, uint32_t batch, LargeShape sh) {
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n, total = per * batch;
-  const unsigned log_mod = sh.logn + 1;
   for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per, ce = i % per;
     const uint32_t c = (uint32_t)(ce >> sh.logn), e = (uint32_t)(ce & (sh.n - 1));
-    const u64 a_raw = lwe_in[b * (n_lwe + 1) + step];
-    u64 a = 0;
-    if (BNF) a = modulus_switch(a_raw, log_mod);
-    else if (a_raw != 0) a = ms_non_native(a_raw, log_mod);
-    const uint32_t full = (uint32_t)(a >> sh.logn) & 1u, rem = (uint32_t)(a & (sh.n - 1));
+    const Monomial xa = mask_monomial<BNF>(lwe_in[b * (n_lwe + 1) + step], sh.logn);
     const u64* ap = acc + b * per + (uint64_t)c * sh.n;
-    u64 v = ap[(e - rem) & (sh.n - 1)];  // mul_assign by X^a: new[e] = old[(e - rem) % N], negated for e < rem
-    if (full ^ (e < rem)) v = neg_q<BNF>(v);
+    u64 v = ap[xa.mul_src(e, sh.n)];  // mul_assign by X^a
+    if (xa.mul_neg(e)) v = neg_q<BNF>(v);
     const u64 ct1 = BNF ? v - ap[e] : sub_custom(v, ap[e]);
     decompose_store<BNF>(ct1, digits + b * sh.level * per + (uint64_t)c * sh.n + e, per, sh.base_log, (int)sh.level);
   }
@@ -132,40 +123,22 @@ __global__ __launch_bounds__(256) void large_rotdec_top(u64* __restrict__ digits
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= cols) return;
   const uint32_t bc = blockIdx.y, b = bc / (sh.k + 1), c = bc % (sh.k + 1);
-  const unsigned log_mod = sh.logn + 1;
-  const u64 a_raw = lwe_in[(uint64_t)b * (n_lwe + 1) + step];
-  u64 a = 0;
-  if (BNF) a = modulus_switch(a_raw, log_mod);
-  else if (a_raw != 0) a = ms_non_native(a_raw, log_mod);
-  const uint32_t full = (uint32_t)(a >> sh.logn) & 1u, rem = (uint32_t)(a & (sh.n - 1));
+  const Monomial xa = mask_monomial<BNF>(lwe_in[(uint64_t)b * (n_lwe + 1) + step], sh.logn);
   const u64* ap = acc + (uint64_t)bc * sh.n;
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n;
   u64* dp = digits + (uint64_t)b * sh.level * per + (uint64_t)c * sh.n + j;
-  u64 st[R];
-  bool sg[R];
+  NttDigits<BNF> dg[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t e = (uint32_t)(j + r * cols);
-    u64 v = ap[(e - rem) & (sh.n - 1)];  // X^a acc: new[e] = old[(e - rem) % N], negated for e < rem
-    if (full ^ (e < rem)) v = neg_q<BNF>(v);
-    const u64 x = BNF ? v - ap[e] : sub_custom(v, ap[e]);
-    if (BNF) {
-      st[r] = decomp_init_native(x, sh.base_log, (int)sh.level);
-      sg[r] = false;
-    } else {  // iter.rs:623-745, as decompose_store
-      const unsigned shift = 64u - (unsigned)(sh.base_log * (int)sh.level);
-      sg[r] = x >= P / 2 + 1;
-      st[r] = closest_abs_nonnative(sg[r] ? P - x : x, sh.base_log, (int)sh.level) >> shift;
-    }
+    u64 v = ap[xa.mul_src(e, sh.n)];  // X^a acc
+    if (xa.mul_neg(e)) v = neg_q<BNF>(v);
+    dg[r].init(BNF ? v - ap[e] : sub_custom(v, ap[e]), sh.base_log, (int)sh.level);
   }
   for (uint32_t li = 0; li < sh.level; ++li) {
     u64 x[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      u64 term = decompose_one_level(sh.base_log, st[r]);
-      if (!BNF && sg[r]) term = (u64)0 - term;
-      x[r] = ((int64_t)term < 0) ? term + P : term;
-    }
+    for (int r = 0; r < R; ++r) x[r] = dg[r].next(sh.base_log);
 #pragma unroll
     for (int s = 0; s < K; ++s) {  // stage s: m = 2^s groups, pair distance 2^(K-1-s) in r; twiddle tw[m + g] = 2^e
       const int d = 1 << (K - 1 - s);
@@ -218,27 +191,18 @@ __device__ __forceinline__ void tile5_fwd_b_tw(u64 (&x)[8], const u64 (&tw)[8]) 
 // decomposition state of its phase-A rows, then per level runs the phase-A stages, the LDS exchange and the phase-B
 // stages and stores the digit polynomial from its phase-B rows.  Grid: x = column tiles of 64, y = GLWE polynomials.
 template <int K, bool BNF, bool ONLY, int W>
-__device__ __forceinline__ void rotdec_tile_body(u64* __restrict__ dp, const u64* __restrict__ ap, uint32_t full,
-                                                 uint32_t rem, uint64_t cols, uint64_t col, uint32_t c, uint64_t per,
+__device__ __forceinline__ void rotdec_tile_body(u64* __restrict__ dp, const u64* __restrict__ ap, Monomial xa,
+                                                 uint64_t cols, uint64_t col, uint32_t c, uint64_t per,
                                                  const LargeShape& sh, const u64* __restrict__ twist, u64* lds) {
   using Rw = tile::Rows<K>;
   constexpr int RPT = Rw::RPT;
-  u64 st[RPT];
-  bool sg[RPT];
+  NttDigits<BNF> dg[RPT];
 #pragma unroll
   for (int k = 0; k < RPT; ++k) {
     const uint32_t e = (uint32_t)(Rw::a(W, k) * cols + col);
-    u64 v = ap[(e - rem) & (sh.n - 1)];  // X^a acc: new[e] = old[(e - rem) % N], negated for e < rem
-    if (full ^ (e < rem)) v = neg_q<BNF>(v);
-    const u64 x = BNF ? v - ap[e] : sub_custom(v, ap[e]);
-    if (BNF) {
-      st[k] = decomp_init_native(x, sh.base_log, (int)sh.level);
-      sg[k] = false;
-    } else {
-      const unsigned shift = 64u - (unsigned)(sh.base_log * (int)sh.level);
-      sg[k] = x >= P / 2 + 1;
-      st[k] = closest_abs_nonnative(sg[k] ? P - x : x, sh.base_log, (int)sh.level) >> shift;
-    }
+    u64 v = ap[xa.mul_src(e, sh.n)];  // X^a acc
+    if (xa.mul_neg(e)) v = neg_q<BNF>(v);
+    dg[k].init(BNF ? v - ap[e] : sub_custom(v, ap[e]), sh.base_log, (int)sh.level);
   }
   u64 tv[ONLY ? RPT : 1];  // the block twist of the lane's phase-B rows: the same for every level
   if constexpr (ONLY) {
@@ -249,11 +213,7 @@ __device__ __forceinline__ void rotdec_tile_body(u64* __restrict__ dp, const u64
   for (uint32_t li = 0; li < sh.level; ++li) {
     u64 x[RPT];
 #pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-      u64 term = decompose_one_level(sh.base_log, st[k]);
-      if (!BNF && sg[k]) term = (u64)0 - term;
-      x[k] = ((int64_t)term < 0) ? term + P : term;
-    }
+    for (int k = 0; k < RPT; ++k) x[k] = dg[k].next(sh.base_log);
     u64* o = dp + (uint64_t)li * per;
     if constexpr (K == 5 && ONLY) {  // r5: phase A, phase B and the block twist as generated asm (gen_tile_asm.py)
       tile5_fwd_a<W>(x);
@@ -285,20 +245,15 @@ __global__ __launch_bounds__(256) void large_rotdec_tile(u64* __restrict__ digit
   const uint32_t c = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t col = (uint64_t)blockIdx.x * 64 + c;
   const uint32_t bc = blockIdx.y, b = bc / (sh.k + 1), cc = bc % (sh.k + 1);
-  const unsigned log_mod = sh.logn + 1;
-  const u64 a_raw = lwe_in[(uint64_t)b * (n_lwe + 1) + step];
-  u64 a = 0;
-  if (BNF) a = modulus_switch(a_raw, log_mod);
-  else if (a_raw != 0) a = ms_non_native(a_raw, log_mod);
-  const uint32_t full = (uint32_t)(a >> sh.logn) & 1u, rem = (uint32_t)(a & (sh.n - 1));
+  const Monomial xa = mask_monomial<BNF>(lwe_in[(uint64_t)b * (n_lwe + 1) + step], sh.logn);
   const u64* ap = acc + (uint64_t)bc * sh.n;
   const uint64_t per = (uint64_t)(sh.k + 1) * sh.n;
   u64* dp = digits + (uint64_t)b * sh.level * per + (uint64_t)cc * sh.n;
   switch (w) {
-    case 0: rotdec_tile_body<K, BNF, ONLY, 0>(dp, ap, full, rem, cols, col, c, per, sh, twist, lds); break;
-    case 1: rotdec_tile_body<K, BNF, ONLY, 1>(dp, ap, full, rem, cols, col, c, per, sh, twist, lds); break;
-    case 2: rotdec_tile_body<K, BNF, ONLY, 2>(dp, ap, full, rem, cols, col, c, per, sh, twist, lds); break;
-    default: rotdec_tile_body<K, BNF, ONLY, 3>(dp, ap, full, rem, cols, col, c, per, sh, twist, lds); break;
+    case 0: rotdec_tile_body<K, BNF, ONLY, 0>(dp, ap, xa, cols, col, c, per, sh, twist, lds); break;
+    case 1: rotdec_tile_body<K, BNF, ONLY, 1>(dp, ap, xa, cols, col, c, per, sh, twist, lds); break;
+    case 2: rotdec_tile_body<K, BNF, ONLY, 2>(dp, ap, xa, cols, col, c, per, sh, twist, lds); break;
+    default: rotdec_tile_body<K, BNF, ONLY, 3>(dp, ap, xa, cols, col, c, per, sh, twist, lds); break;
   }
 }
 
@@ -509,8 +464,7 @@ __global__ __launch_bounds__(256) void large_accumulate(u64* __restrict__ acc, c
 }
 
 // BNF: rotate by -ms(body [+ centered correction]) (ntt64_bnf_pbs.rs:262-270); Solinas: the LUT was pre-rotated;
-// then sample extraction of coefficient 0 (glwe_sample_extraction.rs:89-160): out[c N] = A_c[0],
-// out[c N + j] = -A_c[N - j], out[k N] = B[0]
+// then sample extraction of coefficient 0 (Monomial::extract_*) per mask polynomial, out[k N] = B[0]
 // With io.glwe_out the rotated accumulator itself is stored (blind_rotate_ntt64[_bnf]_assign); skipped items
 // (io.lut_for == NULL) are not written.  lwe_out / glwe_out point at the chunk's first item; b0 is its global index.
 template <bool BNF, bool GLWE>
@@ -523,23 +477,19 @@ __global__ __launch_bounds__(256) void large_extract(u64* __restrict__ lwe_out, 
   for (uint64_t i = grid_stride_start(); i < total; i += grid_stride()) {
     const uint64_t b = i / per_out, o = i % per_out;
     if ((io.lut_idx || GLWE) && !io.lut_for(b0 + b, per)) continue;
-    uint32_t full = 0, rem = 0;
-    if (BNF) {
-      const u64 body = modulus_switch(lwe_in[b * (n_lwe + 1) + n_lwe] + (corr ? corr[b] : 0), sh.logn + 1);
-      full = (uint32_t)(body >> sh.logn) & 1u;
-      rem = (uint32_t)(body & (sh.n - 1));
-    }
+    Monomial xb;
+    if (BNF) xb = Monomial(modulus_switch(lwe_in[b * (n_lwe + 1) + n_lwe] + (corr ? corr[b] : 0), sh.logn + 1), sh.logn);
     const uint32_t c = (uint32_t)(o >> sh.logn), j = (uint32_t)(o & (sh.n - 1));  // o = k N gives c = k, j = 0
-    if (GLWE) {  // new[j] = old[(j + rem) % N], negated for j >= N - rem
-      u64 v = acc[b * per + (uint64_t)c * sh.n + ((j + rem) & (sh.n - 1))];
-      if (full ^ (j >= sh.n - rem)) v = neg_q<BNF>(v);
+    if (GLWE) {
+      u64 v = acc[b * per + (uint64_t)c * sh.n + xb.div_src(j, sh.n)];
+      if (xb.div_neg(j, sh.n)) v = neg_q<BNF>(v);
       lwe_out[i] = v;
       continue;
     }
-    const uint32_t m = (j == 0) ? 0 : sh.n - j;
-    u64 v = acc[b * per + (uint64_t)c * sh.n + ((m + rem) & (sh.n - 1))];
-    if (full ^ (m >= sh.n - rem)) v = neg_q<BNF>(v);
-    lwe_out[i] = (c == sh.k || j == 0) ? v : neg_q<BNF>(v);
+    const uint32_t m = Monomial::extract_src(j, sh.n);  // the body (c = k) has j = 0
+    u64 v = acc[b * per + (uint64_t)c * sh.n + xb.div_src(m, sh.n)];
+    if (xb.div_neg(m, sh.n)) v = neg_q<BNF>(v);
+    lwe_out[i] = Monomial::extract_neg(j) ? neg_q<BNF>(v) : v;
   }
 }
 

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "scratch.hpp"
+#include "core_device.hpp"
 #include "mi_arith.hpp"
 #include "ntt64_launch.hpp"
 #include "pbs_tw_body.hpp"
@@ -22,43 +23,16 @@
 namespace mi {
 namespace pbstw {
 
-static constexpr int N = 2048;
+using core::Monomial;
+using core::modulus_switch;
+using core::neg_custom;
+
+static constexpr int N = 2048, LOGN = 11;
 // per-wave LDS buffer of the blind-rotation kernels (u64): N, padded to a 32 x 66 tile when the bodies run one-pass
 // transposes (tools/gen_pbs_kernel.py PBS_FULL_T); 2 x 16.5 KiB + the 512 B table per workgroup keeps 4 per CU
 static constexpr int NPW = MI_PBS_LDS_STRIDE;
 static_assert(NPW >= N, "a wave buffer holds at least one polynomial");
 static constexpr unsigned LOG_MOD = 12;  // PolynomialSize::to_blind_rotation_input_modulus_log
-
-__device__ __forceinline__ u64 modulus_switch(u64 input, unsigned log_modulus) {  // fft_impl/common.rs:10-23
-  return (input + (1ull << (64u - log_modulus - 1u))) >> (64u - log_modulus);
-}
-
-// algorithms/modulus_switch.rs:60-104 centered_binary_ms_body_correction_to_add (128-lane reduction)
-__device__ u64 centered_body_correction(const u64* __restrict__ lwe, uint32_t n_lwe, int t, u64* sh) {
-  u64 sum_half = 0;
-  int64_t sum_hed = 0;
-  for (uint32_t i = t; i < n_lwe; i += 128) {
-    const u64 a = lwe[i];
-    const int64_t err = (int64_t)((modulus_switch(a, LOG_MOD) << (64u - LOG_MOD)) - a);
-    const int64_t half = err / 2;  // truncating, as Rust's signed division
-    sum_half += (u64)half;
-    sum_hed += 2 * half - err;
-  }
-  sh[t] = sum_half;
-  sh[128 + t] = (u64)sum_hed;
-  __syncthreads();
-  for (int s = 64; s > 0; s >>= 1) {
-    if (t < s) {
-      sh[t] += sh[t + s];
-      sh[128 + t] = (u64)((int64_t)sh[128 + t] + (int64_t)sh[128 + t + s]);
-    }
-    __syncthreads();
-  }
-  const u64 total_half = sh[0];
-  const int64_t total_hed = (int64_t)sh[128];
-  __syncthreads();
-  return total_half - (u64)(total_hed / 2) - (1ull << (64u - LOG_MOD - 1u));
-}
 
 // The forward's lane-pair twiddles (tab[N..N+31]) and the W1'' inverse's last-DIT-stage twiddles (tab[3 (N+32)..],
 // powers of two: the same for the plain and the N^-1-folded untwist) into LDS, read by the bodies' pair stages.
@@ -86,7 +60,7 @@ __global__ __launch_bounds__(128) void pbs_tw_kernel(u64* __restrict__ lwe_out, 
   const u64* lwe = lwe_in + (size_t)b * (n_lwe + 1);
   load_lane_pair_tables(lwtab, tab, t);  // ends with a workgroup barrier
   u64 body_corr = 0;
-  if (centered) body_corr = centered_body_correction(lwe, n_lwe, t, buf);
+  if (centered) body_corr = core::centered_body_correction<128>(lwe, n_lwe, LOG_MOD, t, buf);
 
   const uint32_t S = (uint32_t)(uintptr_t)(buf + w * NPW), SP = (uint32_t)(uintptr_t)(buf + (1 - w) * NPW);
   const u64* lutw = lut + (size_t)w * N;
@@ -103,17 +77,16 @@ __global__ __launch_bounds__(128) void pbs_tw_kernel(u64* __restrict__ lwe_out, 
                      [tab_lo] "s"(tab_lo), [tab_hi] "s"(tab_hi), [bl] "s"(base_log),
                      [LW] "s"((uint32_t)(uintptr_t)lwtab));
   // buf[w NPW + e] = acc_w[e].  Final rotation by -ms(b) (ntt64_bnf_pbs.rs:262-270), then sample
-  // extraction at nth = 0 (glwe_sample_extraction.rs:89-160): out[0] = A'[0], out[j] = -A'[N - j].
+  // extraction at nth = 0 (Monomial::extract_*).
   const u64* acc = buf + w * NPW;
-  const u64 body = modulus_switch(lwe[n_lwe] + body_corr, LOG_MOD);
-  const int full = (int)(body / N) & 1, rem = (int)(body % N);
-  if (io.glwe_out) {  // blind_rotate_ntt64_bnf_assign: the rotated GLWE itself (new[m] = old[(m + rem) % N], signed)
+  const Monomial xb(modulus_switch(lwe[n_lwe] + body_corr, LOG_MOD), LOGN);
+  if (io.glwe_out) {  // blind_rotate_ntt64_bnf_assign: the rotated GLWE itself
     u64* g = io.glwe_out + ((size_t)b * 2 + w) * N;
 #pragma unroll 4
     for (int r = 0; r < 32; ++r) {
       const int m = 64 * r + (int)lane;
-      u64 v = acc[(m + rem) & (N - 1)];
-      if (full ^ (m >= N - rem)) v = (u64)0 - v;
+      u64 v = acc[xb.div_src(m, N)];
+      if (xb.div_neg(m, N)) v = (u64)0 - v;
       g[m] = v;
     }
     return;
@@ -123,38 +96,25 @@ __global__ __launch_bounds__(128) void pbs_tw_kernel(u64* __restrict__ lwe_out, 
 #pragma unroll 4
     for (int r = 0; r < 32; ++r) {
       const int j = 64 * r + (int)lane;
-      const int m = (j == 0) ? 0 : N - j;
-      u64 v = acc[(m + rem) & (N - 1)];
-      if (full ^ (m >= N - rem)) v = (u64)0 - v;
-      out[j] = (j == 0) ? v : (u64)0 - v;
+      const int m = Monomial::extract_src(j, N);
+      u64 v = acc[xb.div_src(m, N)];
+      if (xb.div_neg(m, N)) v = (u64)0 - v;
+      out[j] = Monomial::extract_neg(j) ? (u64)0 - v : v;
     }
   } else if (lane == 0) {
-    u64 v = acc[rem & (N - 1)];
-    if (full) v = (u64)0 - v;
+    u64 v = acc[xb.div_src(0, N)];
+    if (xb.div_neg(0, N)) v = (u64)0 - v;
     out[N] = v;
   }
 }
 
 // ---- Solinas-modulus PBS (ntt64_pbs.rs:213-286, 482-538) on the same engine ---------------------------
-static constexpr u64 P = GL_P;
-__device__ __forceinline__ u64 neg_custom(u64 a) { return a == 0 ? 0 : P - a; }
-
-// ntt64_pbs.rs:540-549 pbs_modulus_switch_non_native (divide_round(a 2N, p), misc.rs:6-18), reduced mod
-// 2N: X^(2N) = 1, so a value that rounds to 2N rotates like 0 (and 0 skips the step, whose CMUX
-// difference would be 0 anyway)
-__device__ __forceinline__ u64 ms_non_native(u64 input) {
-  const unsigned __int128 num = ((unsigned __int128)input) << (LOG_MOD);
-  const u64 nh = (u64)(num >> 64), nl = (u64)num;
-  unsigned __int128 r = (unsigned __int128)nh * GL_EPS + nl;  // num = nh p + r
-  u64 q = nh;
-  while (r >= P) { r -= P; ++q; }
-  return (q + (r >= (P >> 1) ? 1 : 0)) & (2 * N - 1);
-}
-
+// ms_non_native reduced mod 2N: X^(2N) = 1, so a value that rounds to 2N rotates like 0 (and 0 skips the step, whose
+// CMUX difference would be 0 anyway)
 __global__ __launch_bounds__(256) void ms_non_native_kernel(u64* __restrict__ dst, const u64* __restrict__ src,
                                                             uint64_t count) {
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256)
-    dst[i] = ms_non_native(src[i]);
+    dst[i] = core::ms_non_native(src[i], LOG_MOD) & (2 * N - 1);
 }
 
 // switched: batch x (n+1) switched values in [0, 2N) (mask, then body); lut: 2 x N mod p;
@@ -177,13 +137,12 @@ __global__ __launch_bounds__(128) void pbs_tw_sol_kernel(u64* __restrict__ lwe_o
   const u64* msw = switched + (size_t)b * (n_lwe + 1);
   load_lane_pair_tables(lwtab, tab, t);
   {
-    const u64 body = msw[n_lwe] & (2 * N - 1);
-    const int full = (int)(body / N) & 1, rem = (int)(body % N);
+    const Monomial xb(msw[n_lwe], LOGN);
     const u64* l = lut + (size_t)w * N;
     for (int r = 0; r < 32; ++r) {
-      const int m = 64 * r + (int)lane;  // new[m] = old[(m + rem) % N], negated for m >= N - rem
-      u64 v = l[(m + rem) & (N - 1)];
-      if (full ^ (m >= N - rem)) v = neg_custom(v);
+      const int m = 64 * r + (int)lane;
+      u64 v = l[xb.div_src(m, N)];
+      if (xb.div_neg(m, N)) v = neg_custom(v);
       buf[w * NPW + m] = v;
     }
   }
@@ -211,7 +170,8 @@ __global__ __launch_bounds__(128) void pbs_tw_sol_kernel(u64* __restrict__ lwe_o
 #pragma unroll 4
     for (int r = 0; r < 32; ++r) {
       const int j = 64 * r + (int)lane;
-      out[j] = (j == 0) ? acc[0] : neg_custom(acc[N - j]);
+      const u64 v = acc[Monomial::extract_src(j, N)];
+      out[j] = Monomial::extract_neg(j) ? neg_custom(v) : v;
     }
   } else if (lane == 0) {
     out[N] = acc[0];

@@ -330,7 +330,7 @@ class Wave:
             raise NotImplementedError(a)
 
     def _set_exec_or(self, a, m):
-        """SALU write of EXEC (the EXEC-masked arithmetic of gen_tw_kernel); True when a[0] is exec."""
+        """SALU write of EXEC; True when a[0] is exec."""
         if a[0] != "exec":
             return False
         self.exec = m
@@ -471,38 +471,30 @@ def body_lines(hdr, name, prefix="MI_TW_BODY_"):
 
 
 def run_body(hdr, name, poly, twist_tab, fwd=True, out_of_place=False, mem_extra=None, ops_extra=None, out_init=None,
-             w1x=None, record=None):
+             record=None):
     """Emulate one wave (wave 0 of a workgroup) of the transform body on one polynomial.  out_of_place: the body
     writes another buffer (%[o_lo] / %[o_hi], the key-conversion body), which is returned.  mem_extra / ops_extra:
     more memory regions (base address -> u64 array) and operand bindings (the MAC-fused inverse's term bases).
     out_init: the %[o_*] buffer's initial contents (the Ntt64View add_backward bodies read and write it); the call then
     returns (data, out).  record: a CarryRecorder that collects this run's carry outcomes (line indices are those of
-    body_lines(hdr, name)).  w1x (default: the generator's FWD_W1X for forward bodies, i.e. names starting "fwd"): the
-    forward's W1x lane-pair layout (lane = i + 32 j0) and its transpose addresses, as ntt64_tw_device.hpp computes them."""
+    body_lines(hdr, name)).  The per-lane transpose addresses are those of the standalone bodies' W1x lane-pair layout
+    (lane = i + 32 j0; the inverse's W1'' pair bit j5 likewise), as ntt64_tw_device.hpp computes them."""
     data = np.array(poly, dtype=np.uint64).copy()
     tw = np.array(twist_tab, dtype=np.uint64)
     GB, TB, OB = 0x100000000, 0x200000000, 0x300000000
     out = np.zeros_like(data) if out_init is None else np.array(out_init, dtype=np.uint64).copy()
     mem = {GB: data, TB: tw, OB: out}
     lane = np.arange(LANES, dtype=np.uint64)
-    par, i = lane & np.uint64(1), lane >> np.uint64(1)
+    par, i = lane >> np.uint64(5), lane & np.uint64(31)
     S = 0
     ops = {"g_lo": f"{GB & 0xFFFFFFFF}", "g_hi": f"{GB >> 32}", "tw_lo": f"{TB & 0xFFFFFFFF}", "tw_hi": f"{TB >> 32}",
            "o_lo": f"{OB & 0xFFFFFFFF}", "o_hi": f"{OB >> 32}"}
     w = Wave(None, mem)
     w.rec = record
-    vin = {"l8": lane * 8, "t1w": S + (lane & 31) * 8, "t1r": S + (i * 34 + par) * 8, "lwo": par * 128,
-           "t2wl": S + ((i & 15) * 66 + 33 * par) * 8, "t2wh": S + ((i & 15) * 66 + 31 * par + 1) * 8,
-           "t2r": S + (lane ^ (lane >> np.uint64(5))) * 8, "t4w": S + ((i & 15) * 66 + par) * 8, "t4r": S + lane * 8,
+    vin = {"l8": lane * 8, "t1w": S + (lane & 31) * 8, "t1r": S + (i * 33 + par) * 8, "lwo": par * 128,
+           "t2wl": S + ((i & 15) * 65 + 33 * par) * 8, "t2wh": S + ((i & 15) * 65 + 31 * par + 1) * 8,
+           "t2r": S + (lane ^ (lane >> np.uint64(5))) * 8, "t4w": S + ((i & 15) * 65 + par) * 8,
            "t1x": S + (lane + (lane >> np.uint64(5))) * 8, "t1y": S + ((i & 15) * 66 + 33 * par) * 8}
-    if w1x is None:
-        import gen_tw_kernel as _T
-        w1x = (_T.FWD_W1X and name.startswith("fwd")) or (_T.INV_W1X and name.startswith("inv"))
-    if w1x:  # lane = i + 32 j0 (gen_tw_kernel NTT_ADDR_W1X; the inverse's W1'' pair bit j5 likewise)
-        par, i = lane >> np.uint64(5), lane & np.uint64(31)
-        vin.update({"t1r": S + (i * 33 + par) * 8, "lwo": par * 128,
-                    "t2wl": S + ((i & 15) * 65 + 33 * par) * 8, "t2wh": S + ((i & 15) * 65 + 31 * par + 1) * 8,
-                    "t4w": S + ((i & 15) * 65 + par) * 8, "t1y": S + ((i & 15) * 66 + 33 * par) * 8})
     for k, (name_, val) in enumerate(vin.items()):
         w.v[200 + k] = val.astype(np.uint64)   # outside the body's v8..v127
         ops[name_] = f"v{200 + k}"

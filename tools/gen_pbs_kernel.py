@@ -64,14 +64,13 @@ V_T1X = 249   # the W1'' inverse's transpose address S + 8 (lane + (lane >> 5));
 def addr_for(tab):
     return Addr(lambda bt, k, dst: f"global_load_dwordx2 {pv(dst)}, v{VOFF + bt}, {sp(tab)} offset:{512 * k}",
                 t1w=f"v{V_T1W}", t1r=f"v{V_T1R}", t2wl=f"v{V_T2WL}", t2wh=f"v{V_T2WH}", t2r=f"v{V_T2R}",
-                t4w=f"v{V_T4W}", t4r=f"v{V_T4R}", lwo=f"v{V_LWO}", lw=sp(tab), t1x=f"v{V_T1X}", t1y=f"v{V_T2WL}")
+                t4w=f"v{V_T4W}", lwo=f"v{V_LWO}", lw=sp(tab), t1x=f"v{V_T1X}", t1y=f"v{V_T2WL}")
 
 
 # The blind-rotation bodies own 16.5 KiB of LDS per wave (PBS_LDS_STRIDE u64): their forward T1 and inverse W1'' -> W0
 # transposes run in one pass through a 32 x 66 tile (gen_tw_kernel.t1_full) instead of two lane halves with exec flips
 # and three waits.  V_TB = S + 8 (66 (lane >> 1) + (lane & 1)); the tile's other address is V_T4R = S + 8 lane.
-PBS_FULL_T = True
-PBS_LDS_STRIDE = 32 * 66 if PBS_FULL_T else 2048   # u64 per wave buffer (pbs_tw.hip MI_PBS_LDS_STRIDE)
+PBS_LDS_STRIDE = 32 * 66   # u64 per wave buffer (pbs_tw.hip MI_PBS_LDS_STRIDE)
 V_TB = 250
 # the lane-pair twiddles (32 forward + the inverse's 32 last-DIT-stage twiddles of the W1'' layout) live in the
 # workgroup's LDS (copied by pbs_tw.hip at kernel start): lookups at LDS instead of L2 latency.
@@ -85,7 +84,7 @@ def build_addrs():
     FWD_ADDR, INV_ADDR = addr_for(S_TWF), addr_for(S_TWI)
     FWD_ADDR_P, INV_ADDR_P = addr_for(S_TWF), addr_for(S_TWI)
     for a in (FWD_ADDR_P, INV_ADDR_P):
-        a.full_t, a.tfw, a.tfb = PBS_FULL_T, f"v{V_T4R}", f"v{V_TB}"
+        a.full_t, a.tfw, a.tfb = True, f"v{V_T4R}", f"v{V_TB}"
     for a in (FWD_ADDR, FWD_ADDR_P):
         a.lw_load = lambda dst, k: f"ds_read_b64 {pv(dst)}, v{V_LWL} offset:{8 * k}"
     for a in (INV_ADDR, INV_ADDR_P):
@@ -105,7 +104,7 @@ _PBS_MAP = dict(VOFF=192, V_T1W=196, V_T1R=197, V_LWO=198, V_T2WL=199, V_T2WH=20
                 V_S=204, V_PX=205, V_U8=206, V_HHI=207, GBUF=208, PBUF=240, V_LWL=248, V_T1X=249, V_TB=250)
 _EXT_MAP = dict(VOFF=128, V_T1W=132, V_T1R=133, V_LWO=134, V_T2WL=135, V_T2WH=136, V_T2R=137, V_T4W=138, V_T4R=139,
                 V_S=140, V_PX=141, V_U8=142, V_HHI=143, V_LWL=144, V_T1X=145, V_TB=146, PBUF=148, GBUF=96)
-EXT_PBUF2 = 156   # the partner rows' second buffer (MAC_PARTNER_AHEAD) in the ext map
+EXT_PBUF2 = 156   # the partner rows' second buffer (read one chunk ahead, see mac) in the ext map
 EXT_LDS_STRIDE = 1088   # u64 per wave: the half-wave transposes (32 x 34, 16 x 66) and a 16-row exchange half
 
 
@@ -287,11 +286,6 @@ def stage0_signed(B, tabs, dmap, rows=range(16)):
     sched(B, sg)
 
 
-# the rotation's 32 LDS reads issued together (one exposed LDS round trip instead of two): emulator-exact, but BNF
-# 35.9 k -> 35.2 k PBS/s in a one-box A/B (profiles/r3/pbs_rot_all_reads_ab/): off
-ROT_ALL_READS = False
-
-
 def rotate_decompose(B, sol=False):
     """dmap v64..v127 <- decompose(+-acc[(e - a) mod N] - acc[e]); Solinas bodies negate and subtract
     modulo p (polynomial_wrapping_monic_monomial_mul_assign_custom_mod, then the CMUX difference)."""
@@ -299,29 +293,16 @@ def rotate_decompose(B, sol=False):
           f"s_lshr_b32 s{S_FULL}, s{S_AMS}, 11", f"s_sub_u32 s{S_FULL}, 0, s{S_FULL}",
           f"v_subrev_u32 v{V_U8}, s{S_R8}, v{VOFF}")
     B.raw(*[f"ds_write_b64 v{V_T4R}, {pv(ACC + 2 * r)} offset:{512 * r}" for r in range(32)])
-    if ROT_ALL_READS:
-        # all 32 source addresses (v8..v39), all 32 reads in flight, then half 0 computes while half 1 lands
+    for h in range(2):
+        rows = list(range(16 * h, 16 * h + 16))
         sg = Seg()
-        for r in range(32):
-            a = f"v{8 + r}"
+        for q, r in enumerate(rows):
+            a = f"v{8 + q}"
             sg.add(f"v_add_u32 {a}, {512 * r}, v{V_U8}", [f"v{V_U8}"], [a])
             sg.add(f"v_and_b32 {a}, 0x3ff8, {a}", [a], [a])
             sg.add(f"v_add_u32 {a}, %[S], {a}", [a], [a])
         sched(B, sg)
-        B.raw(*[f"ds_read_b64 {pv(64 + 2 * r)}, v{8 + r}" for r in range(32)])
-    for h in range(2):
-        rows = list(range(16 * h, 16 * h + 16))
-        if ROT_ALL_READS:
-            B.raw("s_waitcnt lgkmcnt(15)" if h == 0 else "s_waitcnt lgkmcnt(0)")  # (in order: <= 15 left = rows 0..16)
-        else:
-            sg = Seg()
-            for q, r in enumerate(rows):
-                a = f"v{8 + q}"
-                sg.add(f"v_add_u32 {a}, {512 * r}, v{V_U8}", [f"v{V_U8}"], [a])
-                sg.add(f"v_and_b32 {a}, 0x3ff8, {a}", [a], [a])
-                sg.add(f"v_add_u32 {a}, %[S], {a}", [a], [a])
-            sched(B, sg)
-            B.raw(*[f"ds_read_b64 {pv(64 + 2 * r)}, v{8 + q}" for q, r in enumerate(rows)], "s_waitcnt lgkmcnt(0)")
+        B.raw(*[f"ds_read_b64 {pv(64 + 2 * r)}, v{8 + q}" for q, r in enumerate(rows)], "s_waitcnt lgkmcnt(0)")
         sg = Seg()
         sls = slots_at([8, 16, 24, 32, 40, 48, 56])
         for q, r in enumerate(rows):
@@ -404,12 +385,10 @@ def mac2(sg, m1, m2, x, g1, p, g2):
     sg.add(f"v_cndmask_b32_e64 {xhi}, {a[1]}, {a[5]}, {cb}", [a[1], a[5], cb], [xhi])
 
 
-# The partner's rows of MAC chunk c + 1 are read while chunk c multiplies (a second 4-row buffer in the registers the
-# multiply slots leave free), so each chunk waits only for its GGSW rows, not for an LDS round trip as well.
-MAC_PARTNER_AHEAD = True
-
-
 def mac(B, dmap):
+    """The MAC of the blind-rotation bodies.  The partner's rows of chunk c + 1 are read while chunk c multiplies (a
+    second 4-row buffer in the registers the multiply slots leave free), so each chunk waits only for its GGSW rows,
+    not for an LDS round trip as well."""
     B.raw(*[f"ds_write_b64 v{V_T4R}, {pv(dmap[r])} offset:{512 * r}" for r in range(32)],
           "s_waitcnt lgkmcnt(0)", "s_barrier")
     free = free_blocks_except(dmap)
@@ -419,21 +398,15 @@ def mac(B, dmap):
     ms = [MulSlot(regs[12 * i], SG0 + 6 * i) for i in range(4)]
     # the zero high halves of the product addends, set once for the whole MAC (prod128)
     B.raw(*[f"v_mov_b32 {m.v[z]}, 0" for m in ms for z in (9, 11)])
-    ahead = MAC_PARTNER_AHEAD and len(regs) >= 56
-    pbufs = [PBUF, regs[48]] if ahead else [PBUF]
-    assert not ahead or regs[48:56] == list(range(regs[48], regs[48] + 8)), regs
-    pread = lambda c: [f"ds_read_b64 {pv(pbufs[c % len(pbufs)] + 2 * k)}, v{V_PX} offset:{512 * (4 * c + k)}"
-                       for k in range(4)]
-    if ahead:
-        B.raw(*pread(0))
+    assert len(regs) >= 56 and regs[48:56] == list(range(regs[48], regs[48] + 8)), regs
+    pbufs = [PBUF, regs[48]]
+    pread = lambda c: [f"ds_read_b64 {pv(pbufs[c % 2] + 2 * k)}, v{V_PX} offset:{512 * (4 * c + k)}" for k in range(4)]
+    B.raw(*pread(0))
     for c in range(8):
-        if ahead:
-            # chunk c's partner rows were issued a chunk ago: allow the next chunk's 4 reads to stay in flight
-            nxt = pread(c + 1) if c + 1 < 8 else []
-            B.raw(*nxt, f"s_waitcnt vmcnt({8 if c < 7 else 0}) lgkmcnt({len(nxt)})")
-        else:
-            B.raw(*pread(c), f"s_waitcnt vmcnt({8 if c < 7 else 0}) lgkmcnt(0)")
-        pb = pbufs[c % len(pbufs)]
+        # chunk c's partner rows were issued a chunk ago: allow the next chunk's 4 reads to stay in flight
+        nxt = pread(c + 1) if c + 1 < 8 else []
+        B.raw(*nxt, f"s_waitcnt vmcnt({8 if c < 7 else 0}) lgkmcnt({len(nxt)})")
+        pb = pbufs[c % 2]
         sg = Seg()
         gb = GBUF + 16 * (c % 2)
         for k in range(4):
@@ -485,14 +458,6 @@ def mac_ext(B, dmap):
     B.raw("s_barrier")
 
 
-def w1pp_regs(dmap):
-    """Register plan of the W1'' inverse after the MAC (dmap: rows 0..15 at v96.., rows 16..31 at v64..): the
-    transposed data in v8..v63 + the first four pairs of rows 0..15, the lane-pair twiddles in v64..v71 (rows
-    16.. are in LDS by then), the output's first half in v64.. and its second in v96.."""
-    assert dmap == [96 + 2 * r for r in range(16)] + [64 + 2 * r for r in range(16)], dmap
-    return dict(dst=[8 + 2 * r for r in range(28)] + [96 + 2 * r for r in range(4)], pre_base=64, ybase=64, newhi=96)
-
-
 def modswitch_acc(B, dmap, rows=range(32), acc=None, sls=None):
     """acc += ms_{p -> 2^64}(y) for the rows of y (dmap); acc[r] at `acc` + 2 q for the q-th row (default ACC + 2 r)."""
     sg = Seg()
@@ -539,10 +504,12 @@ def add_acc_sol(B, dmap, rows=range(32), acc=None, sls=None):
 # layout) and the inverse starts from it (gen_tw_kernel.w1p_as_w1pp), so the step does no T2 and no T1'' transpose.
 # The key the body reads is then the private copy in that order (row R, lane L of polynomial position 64 R + L holds
 # NTT-domain coefficient tw_key_index(64 R + L); pbs_tw.hip prepare_tw_key builds it).
+# The external product / CMUX bodies run the same W1' step on a GGSW permuted into that order per call (pbs_tw.hip
+# launch_ext_tw: the caller's Raw / Normalize GGSW stays in the reference's order).
+# Both are facts about the bodies, not choices between paths: the header states them as MI_PBS_W1P / MI_EXT_W1P for
+# pbs_tw.hip, and tests/test_pbs_codegen.py reads them to lay its keys out.
 PBS_W1P = True
-# the blind-rotation loop keeps one register map across its steps, which the renaming of the DPP-select regroup would
-# break: its bodies keep the DPP-move regroup
-T.REGROUP_DPP_SELECT = False
+EXT_W1P = True
 
 
 def tw_key_index(pos):
@@ -551,21 +518,16 @@ def tw_key_index(pos):
     return 64 * (L >> 1) + 32 * (L & 1) + 2 * (R & 15) + (R >> 4)
 
 
-def fwd_mac_inv(B, tabs, dmap0, w1p, full_t=False, ext=False, inv_kw=None):
+def fwd_mac_inv(B, tabs, dmap0, full_t=False, ext=False, inv_kw=None):
     """Forward transform (its stage 0 already run), the MAC with the partner wave and the inverse; returns the output
-    dmap (W0, canonical).  w1p: the MAC and the inverse's input stay in the forward's W1' layout (PBS_W1P).  ext: the
-    ext-map MAC (mac_ext)."""
-    if w1p:
-        fa, ia = (FWD_ADDR_P, INV_ADDR_P) if full_t else (FWD_ADDR, INV_ADDR)
-        dmap = T.fwd_core(B, tabs, dmap0, fa, first_stage=1, stop="last")
-        (mac_ext if ext else mac)(B, dmap)
-        assert dmap == ([64 + 2 * q for q in range(32)] if full_t else
-                        [8 + 2 * q for q in range(16)] + [64 + 2 * q for q in range(16)]), dmap
-        return T.inv_core(B, tabs, dmap, ia, w1pp=True, w1pp_regs=dict(w1p_in=True, pre_base=40, ybase=96, newhi=64),
-                          **(inv_kw or {}))
-    dmap = T.fwd_core(B, tabs, dmap0, FWD_ADDR, first_stage=1)
-    mac(B, dmap)
-    return T.inv_core(B, tabs, dmap, INV_ADDR, w1pp=True, w1pp_regs=w1pp_regs(dmap))
+    dmap (W0, canonical).  The MAC and the inverse's input stay in the forward's W1' layout.  full_t: the one-pass
+    transposes of the blind-rotation bodies; ext: the ext-map MAC (mac_ext)."""
+    fa, ia = (FWD_ADDR_P, INV_ADDR_P) if full_t else (FWD_ADDR, INV_ADDR)
+    dmap = T.fwd_core(B, tabs, dmap0, fa, first_stage=1, stop="last")
+    (mac_ext if ext else mac)(B, dmap)
+    assert dmap == ([64 + 2 * q for q in range(32)] if full_t else
+                    [8 + 2 * q for q in range(16)] + [64 + 2 * q for q in range(16)]), dmap
+    return T.inv_core(B, tabs, dmap, ia, w1pp_regs=dict(w1p_in=True, pre_base=40, ybase=96, newhi=64), **(inv_kw or {}))
 
 
 def gen_pbs(tabs, sol=False):
@@ -598,7 +560,7 @@ def gen_pbs(tabs, sol=False):
     B.raw(*gload(0), *gload(1))
     rotate_decompose(B, sol)
     stage0_signed(B, tabs, [64 + 2 * r for r in range(32)])
-    dmap = fwd_mac_inv(B, tabs, [64 + 2 * r for r in range(32)], PBS_W1P, full_t=PBS_W1P and PBS_FULL_T)
+    dmap = fwd_mac_inv(B, tabs, [64 + 2 * r for r in range(32)], full_t=True)
     if sol:
         add_acc_sol(B, dmap)
     else:
@@ -611,14 +573,6 @@ def gen_pbs(tabs, sol=False):
     B.raw(*[f"ds_write_b64 v{V_T4R}, {pv(ACC + 2 * r)} offset:{512 * r}" for r in range(32)],
           "s_waitcnt lgkmcnt(0)")
     return B
-
-
-# the external product / CMUX bodies: the same W1' step (with the one-pass transposes of PBS_FULL_T) on a GGSW permuted
-# into the body's order per call (pbs_tw.hip launch_ext_tw: the caller's Raw / Normalize GGSW stays in the reference's
-# order).  One-box A/Bs: without the one-pass transposes +0.5 % (profiles/r3/ext_w1p_ab/: the per-call reorder launch
-# costs about what the two skipped transposes saved), with them 27.70 -> 28.02 M products/s, +1.2 %
-# (profiles/r3/ext_w1p_full_t_ab/)
-EXT_W1P = True
 
 
 def gen_ext(tabs, cmux, sol=False):
@@ -688,7 +642,7 @@ def _gen_ext(tabs, cmux, sol):
             stage0_signed(B, tabs, dmap0, rows=range(4 * g, 4 * g + 4))
     # out += y, 16 rows at a time: rows 0..15 (y in v96..) through v8..v39, loaded while the inverse's G1 stages run
     # (which keep to v40..v63 for their scratch), then rows 16..31 (y in v64..) through v96..v127
-    dmap = fwd_mac_inv(B, tabs, dmap0, EXT_W1P, full_t=False, ext=True,
+    dmap = fwd_mac_inv(B, tabs, dmap0, ext=True,
                        inv_kw=dict(g1_busy=range(8, 40), before_g1=load_rows_sub(8, S_OUT, range(16))))
     assert dmap == [96 + 2 * r for r in range(16)] + [64 + 2 * r for r in range(16)], dmap
     for h, base in ((0, 8), (1, 96)):
@@ -700,8 +654,7 @@ def _gen_ext(tabs, cmux, sol):
 
 
 def emit(name, body, sgprs=SGPR_CLOBBER, vgprs=256):
-    clob = ([f'"v{i}"' for i in range(8, vgprs)] + [f'"s{i}"' for i in sgprs] + ['"scc"', '"memory"'] +
-            (['"vcc"'] if T.REGROUP_DPP_SELECT else []))
+    clob = [f'"v{i}"' for i in range(8, vgprs)] + [f'"s{i}"' for i in sgprs] + ['"scc"', '"memory"']
     return (f"// {name}: {body.nvalu} VALU, {len(body.lines)} lines\n"
             f"#define MI_PBS_BODY_{name.upper()}(...) asm volatile(\\\n" +
             "\\\n".join(f'      "{l}\\n"' for l in body.lines) +

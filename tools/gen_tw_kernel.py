@@ -14,8 +14,8 @@ Data path (forward):
   LAST  regroup lane pairs (DPP) -> stage q = 5 with a per-lane twiddle -> canonical
   T2    W1' -> W0 through LDS (halves split by i, row stride 66, column swizzle j ^ (j >> 5))
   STORE W0 rows
-Inverse: LOAD, T1, regroup + first GS stage + regroup back, CYC_INV, T4 (W1 -> W0), UNTWIST, G1_INV,
-canonical, STORE.
+Inverse: LOAD, T1'' (W0 -> W1''), DIT stages 0..4 (CT, shift twiddles), regroup + last DIT stage with a per-lane
+twiddle, T2'' (W1'' -> W0), UNTWIST, G1_INV (GS), STORE.
 
 Usage: python tools/gen_tw_kernel.py > tfhe-rs-main_modified_amd/csrc/ntt64_tw_body.hpp
 """
@@ -37,17 +37,16 @@ def pv(b):
 
 
 class Op:
-    __slots__ = ("text", "reads", "writes", "kind", "cost", "preds", "succs", "prio", "idx", "mask_reads")
+    __slots__ = ("text", "reads", "writes", "kind", "cost", "preds", "succs", "prio", "idx")
 
     def __init__(self, text, reads, writes, kind="valu"):
         self.text, self.kind = text, kind
         self.reads, self.writes = set(), set()
-        self.mask_reads = set()
         for r in reads:
             self.reads.update(expand(r))
         for w in writes:
             self.writes.update(expand(w))
-        m = (text[1] if isinstance(text, list) else text).split()[0]
+        m = text.split()[0]
         if kind == "salu":
             self.cost = 0.0
         elif m in ("v_mov_b32", "v_lshrrev_b32", "v_lshlrev_b32") or kind == "dpp":
@@ -78,7 +77,7 @@ class Line(str):
 
 
 def _origin():
-    f = sys._getframe(2)  # the caller of Seg.add / Seg.add_masked
+    f = sys._getframe(2)  # the caller of Seg.add
     loc = f.f_locals      # the shift exponent(s) mod 96 of the power-of-two multiplies, None elsewhere
     e = loc.get("e") if "e" in loc else ((loc["e0"], loc["e1"]) if "e0" in loc and "e1" in loc else None)
     return f.f_code.co_name, f.f_lineno - f.f_code.co_firstlineno, e
@@ -93,17 +92,7 @@ class Seg:
         self.ops = []
 
     def add(self, text, reads=(), writes=(), kind="valu"):
-        self.ops.append(Op(Line(text, _origin()) if isinstance(text, str) else text, reads, writes, kind))
-
-    def add_masked(self, set_line, set_reads, text, reads=(), writes=()):
-        """One VALU instruction under EXEC = a lane mask the SALU `set_line` writes from the SGPR pairs `set_reads`
-        (carry / borrow masks of earlier VALU ops), EXEC restored to the saved full mask right after.  Scheduled as one
-        unit; the SALU read of the mask obeys the VALU-write -> SALU-read wait state.  Back-to-back masked units drop
-        the restore between them (masked_peephole)."""
-        op = Op([set_line, Line(text, _origin()), EXEC_RESTORE], list(reads) + list(set_reads), writes)
-        for r in set_reads:
-            op.mask_reads.update(expand(r))
-        self.ops.append(op)
+        self.ops.append(Op(Line(text, _origin()), reads, writes, kind))
 
     def schedule(self):
         ops = self.ops
@@ -154,10 +143,8 @@ class Seg:
                     p = prod.get((op, r))
                     if p is None or p.kind == "salu":
                         continue
-                    if r[0] == "s" or r == "vcc":
+                    if r[0] == "s":
                         need = 2 if op.kind == "salu" else 3
-                        if r in op.mask_reads:  # a VALU-written carry mask read by the SALU that sets EXEC
-                            need = max(2, MASK_LATENCY)
                     elif op.kind == "dpp":
                         need = 3
                     else:
@@ -174,31 +161,15 @@ class Seg:
                 out.append("s_nop 0")
                 slot += 1
                 continue
-            if isinstance(best.text, list):
-                out.extend(best.text)
-            else:
-                out.append(best.text)
+            out.append(best.text)
             issued[best] = slot
             slot += 1
             done.add(best)
             remaining.remove(best)
-        return merge_nops(masked_peephole(out))
+        return merge_nops(out)
 
     def emit_in_order(self):
-        out = []
-        for op in self.ops:
-            out.extend(op.text if isinstance(op.text, list) else [op.text])
-        return out
-
-
-def masked_peephole(lines):
-    """Drop an EXEC restore that the next instruction overwrites (two masked units back to back)."""
-    res = []
-    for i, l in enumerate(lines):
-        if l == EXEC_RESTORE and i + 1 < len(lines) and lines[i + 1].split(" ")[1:2] == ["exec,"]:
-            continue
-        res.append(l)
-    return res
+        return [op.text for op in self.ops]
 
 
 def merge_nops(lines):
@@ -284,31 +255,16 @@ def tmul(sg, S, xlo, xhi, xp, sl, tlo, thi):
     return neg
 
 
-def times_2_32_r2(sg, sl):
-    """The r2 form of times_2_32 (carry folded first, then the (y_lo : 0) pair by two moves), kept for A/B runs."""
+def times_2_32(sg, sl):
+    """P1 <- y 2^32 mod p (not canonical, carry in c0) for y = P1 + c0 2^64 (the unfolded result of a shift, carry
+    in c0): the carry is folded first (y = P0, no second wrap: P1 < (2^32 - 1)^2 when c0 is set), then
+    y 2^32 = y_lo 2^32 + y_hi 2^64 = (y_lo : 0) + y_hi EPS, the (y_lo : 0) pair built by two moves."""
     v, P, c = sl.v, sl.P, sl.c
     sg.add(f"v_cndmask_b32_e64 {v[4]}, 0, -1, {c[0]}", [c[0]], [v[4]])
     sg.add(f"v_mad_u64_u32 {P[0]}, {JUNK}, {v[4]}, 1, {P[1]}", [v[4], P[1]], [P[0], JUNK])
     sg.add(f"v_mov_b32 {v[6]}, 0", [], [v[6]])
     sg.add(f"v_mov_b32 {v[7]}, {v[0]}", [v[0]], [v[7]])
     sg.add(f"v_mad_u64_u32 {P[1]}, {c[0]}, {v[1]}, -1, {P[3]}", [v[1], P[3]], [P[1], c[0]])
-
-
-def times_2_32(sg, sl):
-    """P1 <- y 2^32 mod p (not canonical, carry in c0) for y = P1 + c0 2^64 (the unfolded result of a shift, carry
-    in c0): y 2^32 = P1_lo 2^32 + P1_hi 2^64 + c0 2^96 = (P1_lo : 0) + P1_hi EPS - c0.  The -c0 goes into the high
-    word: (P1_lo - c0 : 0) + (P1_hi + c0') EPS with the borrow b of P1_lo - c0 and c0' = c0 & ~b, since EPS - 2^32 = -1
-    (and when P1_lo = 0 the word wraps to 2^32 - 1 with b set: (2^32 - 1) 2^32 = -1 + p).  P1_hi + c0' never wraps
-    (y < 2^63 whenever c0 is set).  5 VALU + 1 SALU instead of folding the carry first (cndmask + mad) and moving
-    y_lo into a (y_lo : 0) pair."""
-    if not CLASS1_FOLD:
-        return times_2_32_r2(sg, sl)
-    v, P, c = sl.v, sl.P, sl.c
-    sg.add(f"v_mov_b32 {v[6]}, 0", [], [v[6]])
-    sg.add(f"v_subb_co_u32_e64 {v[7]}, {c[1]}, {v[2]}, 0, {c[0]}", [v[2], c[0]], [v[7], c[1]])
-    sg.add(f"s_andn2_b64 {c[0]}, {c[0]}, {c[1]}", [c[0], c[1]], [c[0], "scc"], "salu")
-    sg.add(f"v_addc_co_u32_e64 {v[4]}, {JUNK}, {v[3]}, 0, {c[0]}", [v[3], c[0]], [v[4], JUNK])
-    sg.add(f"v_mad_u64_u32 {P[1]}, {c[0]}, {v[4]}, -1, {P[3]}", [v[4], P[3]], [P[1], c[0]])
 
 
 def add_part1(sg, sl, alo, ahi, tlo, thi):
@@ -331,10 +287,7 @@ def pair_of(lo, hi):
 
 def minus_eps(sg, m, c, dp):
     """dp <- dp - EPS where the SGPR mask c is set (a borrow: + p mod 2^64): m = c ? -15 : 0, then
-    dp += m * 0x11111111 (signed 32 x 32 + 64).  EXEC_MASK: one masked v_mad_i64_i32 (m unused)."""
-    if EXEC_MASK:
-        minus_eps_masked(sg, c, dp)
-        return
+    dp += m * 0x11111111 (signed 32 x 32 + 64)."""
     sg.add(f"v_cndmask_b32_e64 {m}, 0, -15, {c}", [c], [m])
     sg.add(f"v_mad_i64_i32 {dp}, {JUNK}, {m}, s{S_X15}, {dp}", [m, dp], [dp, JUNK])
 
@@ -348,18 +301,12 @@ def sub_seq(sg, sl, dlo, dhi, alo, ahi, tlo, thi):
 
 def ct_core(sg, sl, a, b, neg, tsrc=None):
     """t in sl.v2:v3 (or tsrc) canonical; a, b = (lo, hi, pair)."""
-    if EXEC_MASK:
-        if tsrc:
-            assert tsrc == (b[0], b[1]), tsrc
-            return ct_x(sg, sl, a, b, 96 if neg else 0, b_canon=True)
-        return ct_core_x(sg, sl, a, b, neg, (sl.v[2], sl.v[3]))
     alo, ahi, ap = a
     blo, bhi, bp = b
     tlo, thi = tsrc if tsrc else (sl.v[2], sl.v[3])
-    # t may alias b (tsrc: twiddle +-1 on a canonical b): the sum reads it first, and the subtraction that overwrites
-    # b reads each word of it in the instruction that writes that word, so no copy is needed (the list scheduler
-    # keeps the sum's reads ahead of the overwrite: a write waits for every earlier reader of its register)
-    if tsrc and ALIAS_COPY:  # r2 form (tools/variant_probe A/B)
+    # t may alias b (tsrc: twiddle +-1 on a canonical b): it is copied before the subtraction overwrites b.  Without
+    # the copy the subtraction sits right behind the add on the same registers: measured slower (DESIGN.md §4)
+    if tsrc:
         sg.add(f"v_mov_b32 {sl.v[2]}, {tlo}", [tlo], [sl.v[2]])
         sg.add(f"v_mov_b32 {sl.v[3]}, {thi}", [thi], [sl.v[3]])
         tlo, thi = sl.v[2], sl.v[3]
@@ -376,8 +323,6 @@ def ct_core_canon(sg, sl, a, b, neg):
     """ct_core for a canonical a and the canonical t in sl.v2:v3, with canonical outputs: the difference of
     two canonical values needs only the borrow fix (sub_seq), and their sum is canonical after one select
     between s and U = s + EPS (U when the add carried, s + 2^64 = U mod p, or when U carried, s >= p)."""
-    if EXEC_MASK:
-        return ct_core_x(sg, sl, a, b, neg, (sl.v[2], sl.v[3]), canon_out=True)
     alo, ahi, ap = a
     blo, bhi, bp = b
     v, P, c = sl.v, sl.P, sl.c
@@ -396,23 +341,8 @@ def ct_core_canon(sg, sl, a, b, neg):
 
 
 def ct(sg, sl, a, b, S):
-    if EXEC_MASK:
-        return ct_x(sg, sl, a, b, S)
     neg = tmul(sg, S, b[0], b[1], b[2], sl, sl.v[2], sl.v[3])
     ct_core(sg, sl, a, b, neg)
-
-
-def gs_core(sg, sl, a, b):
-    """a' = a + b, b <- a - b (both semi in, semi out); b canonicalised first."""
-    alo, ahi, ap = a
-    blo, bhi, bp = b
-    v, P, c = sl.v, sl.P, sl.c
-    sg.add(f"v_mad_u64_u32 {P[3]}, {c[1]}, -1, 1, {bp}", [bp], [P[3], c[1]])
-    sg.add(f"v_cndmask_b32_e64 {v[2]}, {blo}, {v[6]}, {c[1]}", [blo, v[6], c[1]], [v[2]])
-    sg.add(f"v_cndmask_b32_e64 {v[3]}, {bhi}, {v[7]}, {c[1]}", [bhi, v[7], c[1]], [v[3]])
-    add_part1(sg, sl, alo, ahi, v[2], v[3])
-    sub_seq(sg, sl, blo, bhi, alo, ahi, v[2], v[3])
-    add_part2(sg, sl, ap)
 
 
 def gs(sg, sl, a, b, S, ac=False, bc=False):
@@ -424,8 +354,6 @@ def gs(sg, sl, a, b, S, ac=False, bc=False):
     same one), so the new b is always the canonical, positive tmul magnitude: no negation is ever
     emitted.  When both inputs are canonical the sum is made canonical too (one select after the add:
     +1 VALU, and the next stage needs no canonicalisation).  Returns (new a canonical, new b canonical)."""
-    if EXEC_MASK:
-        return gs_x(sg, sl, a, b, S, ac, bc)
     alo, ahi, ap = a
     blo, bhi, bp = b
     v, P, c = sl.v, sl.P, sl.c
@@ -463,8 +391,7 @@ def scaled_ct(sg, sl, dmap, ra, rb, S, mode, scales, canon):
     """CT butterfly on logical registers (ra, rb), twiddle 2^S, inputs carrying the scales (ea, eb) (register r holds
     2^scales[r] times its value).  Mode 0: t = 2^(S + ea - eb) b, outputs a + t / a - t of scale ea.  Mode 1:
     t = 2^(eb - S - ea) a, outputs t + b = 2^(eb - S) (a + 2^S b) to position ra and b - t = -2^(eb - S) (a - 2^S b)
-    to position rb (scale eb - S + 96), each into the register of its position (under EXEC_MASK the two logical
-    registers swap their physical ones instead)."""
+    to position rb (scale eb - S + 96), each into the register of its position."""
     ea, eb = scales[ra], scales[rb]
     a, b = X(dmap, ra), X(dmap, rb)
     if mode == 0:
@@ -474,13 +401,6 @@ def scaled_ct(sg, sl, dmap, ra, rb, S, mode, scales, canon):
         else:
             ct(sg, sl, a, b, m)
         scales[ra] = scales[rb] = ea % 192
-    elif EXEC_MASK:  # the masked primitives write the sum into their first operand: the logical registers swap
-        m = (eb - S - ea) % 192
-        if m % 96 == 0 and canon[ra]:
-            ct_core(sg, sl, b, a, m >= 96, tsrc=(a[0], a[1]))
-        else:
-            ct(sg, sl, b, a, m)
-        dmap[ra], dmap[rb] = dmap[rb], dmap[ra]
     else:
         # ct_core's neg flag exchanges which register receives the sum: with it flipped, b + t lands in a's register
         # and b - t in b's, so the register map is unchanged (the PBS bodies' fixed MAC / inverse layout needs that)
@@ -502,28 +422,6 @@ def gmul(sg, ms, x, wlo, whi, olo, ohi, zero_hi=True):
     v, P, c = ms.v, ms.P, ms.c
     PA, PB, PC, PD, Z1, Z2 = P
     A0, A1, B0, B1, C0, C1, D0, D1, Z1l, Z1h, Z2l, Z2h = v
-    if EXEC_MASK:
-        # the same product; R = T + H0 EPS goes straight into o (every read of x is earlier), the borrow fix and
-        # the canonicalising select are EXEC-masked single instructions (13 VALU)
-        op = pair_of(olo, ohi)
-        if zero_hi:
-            sg.add(f"v_mov_b32 {Z1h}, 0", [], [Z1h])
-            sg.add(f"v_mov_b32 {Z2h}, 0", [], [Z2h])
-        sg.add(f"v_mad_u64_u32 {PA}, {JUNK}, {xlo}, {wlo}, 0", [xlo, wlo], [PA, JUNK])
-        sg.add(f"v_mov_b32 {Z1l}, {A1}", [A1], [Z1l])
-        sg.add(f"v_mad_u64_u32 {PB}, {JUNK}, {xlo}, {whi}, {Z1}", [xlo, whi, Z1], [PB, JUNK])
-        sg.add(f"v_mov_b32 {Z2l}, {B0}", [B0], [Z2l])
-        sg.add(f"v_mov_b32 {Z1l}, {B1}", [B1], [Z1l])
-        sg.add(f"v_mad_u64_u32 {PC}, {JUNK}, {xhi}, {wlo}, {Z2}", [xhi, wlo, Z2], [PC, JUNK])
-        sg.add(f"v_mad_u64_u32 {PD}, {JUNK}, {xhi}, {whi}, {Z1}", [xhi, whi, Z1], [PD, JUNK])
-        sg.add(f"v_mad_u64_u32 {PB}, {JUNK}, {C1}, 1, {PD}", [C1, PD], [PB, JUNK])          # H = D + C.hi
-        sg.add(f"v_sub_co_u32_e64 {D0}, {c[0]}, {A0}, {B1}", [A0, B1], [D0, c[0]])          # T = L - H1
-        sg.add(f"v_subb_co_u32_e64 {D1}, {c[1]}, {C0}, 0, {c[0]}", [C0, c[0]], [D1, c[1]])
-        minus_eps_masked(sg, c[1], PD)
-        sg.add(f"v_mad_u64_u32 {op}, {c[0]}, {B0}, -1, {PD}", [B0, PD], [op, c[0]])         # R = T + H0 EPS
-        sg.add(f"v_mad_u64_u32 {PC}, {c[1]}, -1, 1, {op}", [op], [PC, c[1]])                # U = R + EPS
-        mov64_masked(sg, ("or", c[1], c[0]), op, PC)
-        return
     if zero_hi:
         sg.add(f"v_mov_b32 {Z1h}, 0", [], [Z1h])
         sg.add(f"v_mov_b32 {Z2h}, 0", [], [Z2h])
@@ -548,10 +446,6 @@ def gmul(sg, ms, x, wlo, whi, olo, ohi, zero_hi=True):
 def canon(sg, sl, x):
     xlo, xhi, xp = x
     v, P, c = sl.v, sl.P, sl.c
-    if EXEC_MASK:
-        sg.add(f"v_mad_u64_u32 {P[0]}, {c[1]}, -1, 1, {xp}", [xp], [P[0], c[1]])
-        mov64_masked(sg, c[1], xp, P[0])
-        return
     sg.add(f"v_mad_u64_u32 {P[0]}, {c[1]}, -1, 1, {xp}", [xp], [P[0], c[1]])
     sg.add(f"v_cndmask_b32_e64 {xlo}, {xlo}, {v[0]}, {c[1]}", [xlo, v[0], c[1]], [xlo])
     sg.add(f"v_cndmask_b32_e64 {xhi}, {xhi}, {v[1]}, {c[1]}", [xhi, v[1], c[1]], [xhi])
@@ -561,185 +455,16 @@ def canon(sg, sl, x):
 # The scale plan (r5, tools/tw_scale_plan.py): the forward's in-register butterfly networks carry power-of-two scales
 # that the twist table absorbs, so each butterfly may multiply whichever input makes the cheaper shift class.  The
 # plan's table side (ntt64_tw_tables.hpp TW_G1_OUT_SCALE / TW_CYC_IN_SCALE) is generated from the same JSON.
-SCALE_PLAN = True
 _PLAN = None
 
 
 def scale_plan():
     global _PLAN
-    if not SCALE_PLAN:
-        return None
     if _PLAN is None:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import tw_scale_plan
         _PLAN = tw_scale_plan.load()
     return _PLAN
-
-
-# ------------------------------------------------------------------------------------------------
-# EXEC-masked arithmetic (r5).  Every conditional step of the Goldilocks arithmetic (fold a carry: + EPS; fix a
-# borrow: - EPS; canonicalise: select x + EPS) was a VALU select (v_cndmask on the carry mask, 4.3 cycles per 32-bit
-# word) feeding a multiply-add, or a pair of selects.  Here the carry mask goes into EXEC through the SALU (off the
-# VALU issue path) and the step is ONE VALU instruction on the lanes that need it: a fold or a borrow fix is one
-# v_mad (4.6 instead of 8.9 cycles), a select one v_mov_b64 (4.2 instead of 8.6).  Every result is written in
-# place, so the butterflies also need no sum / difference temporaries.  The arithmetic is unchanged: same values,
-# lane by lane (the emulator tests and the GPU parity tests check it).
-EXEC_MASK = False  # measured slower on MI355X (r5, tools/variant_probe): see DESIGN.md §4
-MASK_LATENCY = 2   # list-scheduler slots between a VALU carry write and the SALU EXEC write that reads it
-
-
-def cond_exec(cond):
-    """(SALU line writing EXEC, SGPR pairs it reads) for cond = an SGPR pair, ("or", c1, c0) or ("not", c)."""
-    if isinstance(cond, tuple):
-        if cond[0] == "or":
-            return f"s_or_b64 exec, {cond[1]}, {cond[2]}", [cond[1], cond[2]]
-        return f"s_not_b64 exec, {cond[1]}", [cond[1]]
-    return f"s_mov_b64 exec, {cond}", [cond]
-
-
-def mov64_masked(sg, cond, dst, src):
-    """dst <- src (u64 pairs) on the lanes of cond."""
-    line, sr = cond_exec(cond)
-    sg.add_masked(line, sr, f"v_mov_b64 {dst}, {src}", [src, dst], [dst])
-
-
-def plus_eps_masked(sg, cond, dp):
-    """dp += EPS on the lanes of cond (the fold of a carry out of bit 64: 2^64 = EPS mod p)."""
-    line, sr = cond_exec(cond)
-    sg.add_masked(line, sr, f"v_mad_u64_u32 {dp}, {JUNK}, -1, 1, {dp}", [dp], [dp, JUNK])
-
-
-def minus_eps_masked(sg, cond, dp):
-    """dp -= EPS on the lanes of cond (a borrow out of bit 64: d - 2^64 = d - EPS mod p); -15 * 0x11111111 = -EPS."""
-    line, sr = cond_exec(cond)
-    sg.add_masked(line, sr, f"v_mad_i64_i32 {dp}, {JUNK}, -15, s{S_X15}, {dp}", [dp], [dp, JUNK])
-
-
-def tmul_x(sg, S, x, sl, T, copy_u=False):
-    """T (an aligned pair, may be x itself) <- canonical t with x * 2^S = (neg ? -t : t); returns neg.  Scratch: the
-    slot's P0, v4 and (class 1) P3, carry pairs c0 / c1.  The raw product goes straight into T, so x may be T: every
-    read of x precedes the first write of T in program order (the scheduler keeps that order)."""
-    xlo, xhi, xp = x
-    tlo, thi = T
-    tp = pair_of(tlo, thi)
-    e = S % 96
-    neg = (S >= 96) != (e >= 64)
-    v, P, c = sl.v, sl.P, sl.c
-    if e == 0:
-        if tp == xp:
-            canon(sg, sl, x)
-        else:
-            sg.add(f"v_mad_u64_u32 {tp}, {c[1]}, -1, 1, {xp}", [xp], [tp, c[1]])   # T = x + EPS
-            mov64_masked(sg, ("not", c[1]), tp, xp)                                # x < p: T = x
-        return neg
-    if e < 64:
-        r = e if e <= 32 else e - 32
-        sg.add(f"v_lshlrev_b64 {P[0]}, {r}, {xp}", [xp], [P[0]])
-        if r == 32:
-            h = xhi
-        else:
-            h = v[4]
-            sg.add(f"v_lshrrev_b32 {h}, {32 - r}, {xhi}", [xhi], [h])
-        sg.add(f"v_mad_u64_u32 {tp}, {c[0]}, {h}, -1, {P[0]}", [h, P[0]], [tp, c[0]])   # x 2^r = T + c0 2^64
-        if e > 32:
-            # y = x 2^r folded (T < (2^32 - 1)^2 when c0: no second wrap), then y 2^32 = (y_lo << 32) + y_hi EPS
-            plus_eps_masked(sg, c[0], tp)
-            sg.add(f"v_lshlrev_b64 {P[3]}, 32, {tp}", [tp], [P[3]])
-            sg.add(f"v_mad_u64_u32 {tp}, {c[0]}, {thi}, -1, {P[3]}", [thi, P[3]], [tp, c[0]])
-        sg.add(f"v_mad_u64_u32 {P[0]}, {c[1]}, -1, 1, {tp}", [tp], [P[0], c[1]])        # U = T + EPS
-        mov64_masked(sg, ("or", c[1], c[0]), tp, P[0])                                  # canonical: U if a carry
-        return neg
-    K = 96 - e
-    sg.add(f"v_lshrrev_b64 {P[0]}, {K}, {xp}", [xp], [P[0]])
-    if K == 32 and tp != xp:
-        u = xlo
-    else:
-        u = v[4]
-        if K == 32:
-            sg.add(f"v_mov_b32 {u}, {xlo}", [xlo], [u])
-        else:
-            sg.add(f"v_lshlrev_b32 {u}, {32 - K}, {xlo}", [xlo], [u])
-    sg.add(f"v_mad_u64_u32 {tp}, {JUNK}, {u}, 1, {P[0]}", [u, P[0]], [tp, JUNK])
-    sg.add(f"v_sub_co_u32_e64 {thi}, {c[0]}, {thi}, {u}", [thi, u], [thi, c[0]])
-    minus_eps_masked(sg, c[0], tp)
-    return neg
-
-
-def ct_core_x(sg, sl, a, b, neg, t, canon_out=False):
-    """In-place CT butterfly with the canonical t (= w b, or its negation when neg): not neg: b <- a - t, a <- a + t;
-    neg: b <- a + t, a <- a - t.  The destination of the first result is dead (its value is in t), so nothing needs a
-    temporary.  canon_out (a canonical): both outputs canonical (the sum by a select between s and s + EPS)."""
-    alo, ahi, ap = a
-    blo, bhi, bp = b
-    tlo, thi = t
-    c = sl.c
-    S, D = (b, a) if neg else (a, b)
-
-    def diff(dst):
-        sg.add(f"v_sub_co_u32_e64 {dst[0]}, {c[0]}, {alo}, {tlo}", [alo, tlo], [dst[0], c[0]])
-        sg.add(f"v_subb_co_u32_e64 {dst[1]}, {c[1]}, {ahi}, {thi}, {c[0]}", [ahi, thi, c[0]], [dst[1], c[1]])
-        minus_eps_masked(sg, c[1], dst[2])
-
-    def add(dst):
-        sg.add(f"v_add_co_u32_e64 {dst[0]}, {c[2]}, {alo}, {tlo}", [alo, tlo], [dst[0], c[2]])
-        sg.add(f"v_addc_co_u32_e64 {dst[1]}, {c[2]}, {ahi}, {thi}, {c[2]}", [ahi, thi, c[2]], [dst[1], c[2]])
-        if canon_out:
-            P3 = sl.P[3]
-            sg.add(f"v_mad_u64_u32 {P3}, {c[0]}, -1, 1, {dst[2]}", [dst[2]], [P3, c[0]])
-            mov64_masked(sg, ("or", c[0], c[2]), dst[2], P3)
-        else:
-            plus_eps_masked(sg, c[2], dst[2])
-
-    # the dead destination first (b, whose value t carries), then the other one in place
-    if neg:
-        add(S)
-        diff(D)
-    else:
-        diff(D)
-        add(S)
-
-
-def ct_x(sg, sl, a, b, S, b_canon=False):
-    """CT butterfly (a, b) with twiddle 2^S: t = 2^S b canonical in the slot's P1, then ct_core_x."""
-    t = (sl.v[2], sl.v[3])
-    if S % 96 == 0 and b_canon:
-        sg.add(f"v_mov_b64 {sl.P[1]}, {b[2]}", [b[2]], [sl.P[1]])
-        neg = S >= 96
-    else:
-        neg = tmul_x(sg, S, b, sl, t)
-    ct_core_x(sg, sl, a, b, neg, t)
-
-
-def gs_x(sg, sl, a, b, S, ac=False, bc=False):
-    """EXEC-masked gs (same contract): the difference goes to the slot's P1, the sum into a in place, then
-    b <- |w| (difference) canonical (tmul_x from P1 into b)."""
-    alo, ahi, ap = a
-    blo, bhi, bp = b
-    c, P = sl.c, sl.P
-    dl, dh, dpair = sl.v[2], sl.v[3], P[1]
-    e = S % 96
-    neg = (S >= 96) != (e >= 64)
-    both = ac and bc
-    if not both:
-        if neg and not ac:
-            canon(sg, sl, a)
-        if not neg and not bc:
-            canon(sg, sl, b)
-    # difference (the subtrahend is canonical): a - b, or b - a when the twiddle is negative
-    m, s_ = (b, a) if neg else (a, b)
-    sg.add(f"v_sub_co_u32_e64 {dl}, {c[0]}, {m[0]}, {s_[0]}", [m[0], s_[0]], [dl, c[0]])
-    sg.add(f"v_subb_co_u32_e64 {dh}, {c[1]}, {m[1]}, {s_[1]}, {c[0]}", [m[1], s_[1], c[0]], [dh, c[1]])
-    minus_eps_masked(sg, c[1], dpair)
-    # sum into a in place
-    sg.add(f"v_add_co_u32_e64 {alo}, {c[2]}, {alo}, {blo}", [alo, blo], [alo, c[2]])
-    sg.add(f"v_addc_co_u32_e64 {ahi}, {c[2]}, {ahi}, {bhi}, {c[2]}", [ahi, bhi, c[2]], [ahi, c[2]])
-    if both:
-        sg.add(f"v_mad_u64_u32 {P[3]}, {c[0]}, -1, 1, {ap}", [ap], [P[3], c[0]])
-        mov64_masked(sg, ("or", c[0], c[2]), ap, P[3])
-    else:
-        plus_eps_masked(sg, c[2], ap)
-    tmul_x(sg, S, (dl, dh, dpair), sl, (blo, bhi))
-    return both, True
 
 
 # ------------------------------------------------------------------------------------------------
@@ -805,8 +530,7 @@ class Body:
                 canon[r] = canon[r + dist] = False
             else:
                 canon[r], canon[r + dist] = gs(sg, sl, a, b, S, canon[r], canon[r + dist])
-            self.bfly.setdefault((self.tag, S % 192), []).append(
-                [t for op in sg.ops[n0:] for t in (op.text if isinstance(op.text, list) else [op.text])])
+            self.bfly.setdefault((self.tag, S % 192), []).append([op.text for op in sg.ops[n0:]])
             bf += 1
         for i, op in enumerate(sg.ops):
             op.idx = i
@@ -847,13 +571,6 @@ S_TB = 86    # s[86:93]: table bases
 S_PAR = 20   # s[20:21]: odd-lane mask
 S_X15 = 27   # s27 = 0x11111111 = EPS / 15: d - EPS = d + (-15) * 0x11111111 in one v_mad_i64_i32
 S_EXE = 22   # s[22:23]: saved exec
-EXEC_RESTORE = f"s_mov_b64 exec, s[{S_EXE}:{S_EXE + 1}]"
-
-
-def bases(body, reg_g, dst):
-    for m in range(4):
-        body.raw(f"s_add_u32 s{dst + 2 * m}, {reg_g}[0], {4096 * m}")
-    # (replaced below by proper lo/hi handling)
 
 
 def gen_bases(src, dst):
@@ -871,19 +588,6 @@ def gen_bases(src, dst):
 # boundary), sc1 alone about half of that, nt sc1 10 % slower; loads keep the default policy (nt loads were slower)
 LOAD_POLICY = ""
 STORE_POLICY = " sc0 sc1"
-# Two instruction cuts were tried in r3 and are OFF: tools/variant_probe timed them in one process against the r2 bodies
-# (profiles/r3/variant_probe_r3_changes.txt): the forward with both is 1.2 % slower (58.6 vs 57.9 us per 8192-poly
-# launch) although it issues 2.8 % fewer VALU cycles by the model; the inverse is unchanged.  Dropping the two moves puts
-# the subtraction right behind the add on the same registers, and the fold puts an SALU op inside the carry chain, so
-# both lengthen the dependent chains the 4 resident waves per SIMD must hide.
-ALIAS_COPY = True    # copy a +-1-twiddle operand before the subtraction overwrites it (2 moves; False saves them)
-CLASS1_FOLD = False  # class-1 shifts: True folds the first carry into the 2^32 step (times_2_32) instead
-INV_CYC_DIT = True   # inverse cyclic blocks by decimation in time (dit_exps); False: the GS form
-PROGRESSIVE = True   # forward: start the first stage as the data rows arrive (4 waits) instead of one vmcnt(0):
-                     # 0.6 % faster (tools/variant_probe); the same per row in the inverse's T1 was 0.8 % slower
-PROGRESSIVE_INV = False
-FWD_STORE = "t2"     # forward output: "t2" LDS transpose to W0 + coalesced rows; "x2" / "x4": each lane stores its
-                     # 32 consecutive outputs from the lane-pair layout directly (8- / 16-byte stores, %[pso])
 
 
 def load_rows(dmap, base, voff="%[l8]"):
@@ -930,39 +634,30 @@ class Addr:
         self.__dict__.update(regs)
 
 
+# The standalone bodies' W1x layout (r6): the lane pair of block i is lanes i and i + 32 (lane = i + 32 j0; the inverse's
+# W1'' pair bit j5 likewise) instead of 2 i and 2 i + 1, so the lane-pair stage's regroup is two v_permlane32_swap_b32
+# per register pair (a half-wave exchange, 8.2 cycles each) instead of four DPP moves and four selects (34.8 cycles).
+# Its transposes: T1 with row stride 33 (reads at (i 33 + j0 + 2 q) 8: conflict-free for both 32-lane groups), T2 with
+# row stride 65 and the halves split by i < 16 (lanes 0-15 and 32-47).  The per-lane addresses come from the kernel
+# wrapper (ntt64_tw_device.hpp tw_body: i = lane & 31, j0 = lane >> 5); the odd-lane mask s[S_PAR] is the upper
+# half-wave.  Bodies with their own Addr and no `w1x` (tools/gen_pbs_kernel.py) keep the pairs 2 i, 2 i + 1.
 NTT_ADDR = Addr(lambda bt, k, dst: f"global_load_dwordx2 {pv(dst)}, %[l8], s[{S_TB + 2 * bt}:{S_TB + 2 * bt + 1}] "
-                                   f"offset:{512 * k}",
-                **{n: f"%[{n}]" for n in ("t1w", "t1r", "t2wl", "t2wh", "t2r", "t4w", "t4r", "lwo", "lw", "t1x", "t1y")})
-
-# The forward's W1x layout (r6): the lane pair of block i is lanes i and i + 32 (lane = i + 32 j0) instead of 2 i and
-# 2 i + 1, so the lane-pair stage's regroup is two v_permlane32_swap_b32 per register pair (a half-wave exchange,
-# 8.2 cycles each) instead of four DPP moves and four selects (34.8 cycles).  Its transposes: T1 with row stride 33
-# (reads at (i 33 + j0 + 2 q) 8: conflict-free for both 32-lane groups), T2 with row stride 65 and the halves split by
-# i < 16 (lanes 0-15 and 32-47).  The per-lane addresses come from the kernel wrapper (ntt64_tw_device.hpp tw_body:
-# i = lane & 31, j0 = lane >> 5); the odd-lane mask s[S_PAR] becomes the upper half-wave.
-FWD_W1X = True
-INV_W1X = True   # the standalone inverse bodies' W1'' blocks in the same half-wave pairing (lane = i + 32 j5)
-NTT_ADDR_W1X = Addr(NTT_ADDR.tw_load, w1x=True,
-                    **{n: f"%[{n}]" for n in ("t1w", "t1r", "t2wl", "t2wh", "t2r", "t4w", "t4r", "lwo", "lw", "t1x", "t1y")})
-
-
-def par_mask(ad):
-    """s[S_PAR:S_PAR+1] = the lanes holding the odd member of each lane pair."""
-    if getattr(ad, "w1x", False):
-        return [f"s_mov_b32 s{S_PAR}, 0", f"s_mov_b32 s{S_PAR + 1}, -1"]
-    return [f"s_mov_b32 s{S_PAR}, 0xaaaaaaaa", f"s_mov_b32 s{S_PAR + 1}, 0xaaaaaaaa"]
+                                   f"offset:{512 * k}", w1x=True,
+                **{n: f"%[{n}]" for n in ("t1w", "t1r", "t2wl", "t2wh", "t2r", "t4w", "lwo", "lw", "t1x", "t1y")})
+# s[S_PAR:S_PAR+1] = the lanes holding the odd member of each lane pair in that layout
+PAR_MASK = [f"s_mov_b32 s{S_PAR}, 0", f"s_mov_b32 s{S_PAR + 1}, -1"]
 
 
 FULL_STRIDE = 66  # row stride (u64) of the one-pass transposes of a wave with a 16.5 KiB LDS buffer (ad.full_t)
 
 
-def t1_full(body, dmap, ad, written=False):
+def t1_full(body, dmap, ad):
     """W0 -> W1 in one pass through a 32 x 66 (u64) LDS tile: lane j writes its 32 rows at i 66 + j (%[tfw] = S + 8 lane,
     row in the offset field), lane 2 i + j0 reads element j = 2 q + j0 of row i into register q (%[tfb] = S + 8 (66 i + j0),
     q in the offset field).  Both sides conflict-free (the reads' 64-bank pattern is 4 i + 2 j0).  For waves that own
     16.5 KiB of LDS (the blind rotation); the 8.5 KiB standalone waves run the two-half t1.  The data stays in the same
     registers (every write has landed before the first read)."""
-    L = [] if written else t1_full_writes(dmap, ad, range(32))
+    L = [f"ds_write_b64 {ad.tfw}, {pv(dmap[r])} offset:{r * FULL_STRIDE * 8}" for r in range(32)]
     L.append("s_waitcnt lgkmcnt(0)")
     L += [f"ds_read_b64 {pv(dmap[q])}, {ad.tfb} offset:{q * 16}" for q in range(32)]
     L.append("s_waitcnt lgkmcnt(0)")
@@ -970,31 +665,14 @@ def t1_full(body, dmap, ad, written=False):
     return list(dmap)
 
 
-def t1_full_writes(dmap, ad, rows):
-    return [f"ds_write_b64 {ad.tfw}, {pv(dmap[r])} offset:{r * FULL_STRIDE * 8}" for r in rows]
-
-
-# The one-pass transposes of the blind rotation overlap their LDS traffic with the neighbouring multiplies: the forward's
-# T1 writes each twist batch's 8 rows right after they are multiplied, the inverse's W1'' -> W0 writes each half of the
-# lane-pair DIT stage's registers as soon as that half is done, and the untwist's batches wait only for the rows they use.
-# Built at the end of round 3 and emulator-exact (its waits are not emulated: checked by reasoning only).  One-box A/B:
-# BNF 35.2 k vs 35.3 k PBS/s (noise of +-1.5 k between repeats), Solinas equal (profiles/r3/pbs_progressive_full_t_ab/):
-# no measurable gain, not GPU-parity-tested, so off and the bodies stay byte-identical to the measured ones.
-PROGRESSIVE_FULL_T = False
-
-
-def t1(body, dmap, ybase, newhi, ad=NTT_ADDR, row_waits=None):
-    """W0 -> W1 (split by j half).  Returns the new dmap (x[q] in y for q < 16, x[16+q] at newhi).
-    row_waits: a wait line before each first-half row write (rows written as their loads land)."""
+def t1(body, dmap, ybase, newhi, ad):
+    """W0 -> W1 (split by j half).  Returns the new dmap (x[q] in y for q < 16, x[16+q] at newhi)."""
     if getattr(ad, "full_t", False):
-        assert row_waits is None
         return t1_full(body, dmap, ad)
     L = []
     st = 33 if getattr(ad, "w1x", False) else 34  # row stride (u64): conflict-free reads in either lane-pair layout
     L += [f"s_mov_b32 exec_lo, -1", f"s_mov_b32 exec_hi, 0"]
     for r in range(32):
-        if row_waits:
-            L.append(row_waits[r])
         L.append(f"ds_write_b64 {ad.t1w}, {pv(dmap[r])} offset:{r * st * 8}")
     L += EXEC_ALL
     for q in range(16):
@@ -1011,111 +689,52 @@ def t1(body, dmap, ybase, newhi, ad=NTT_ADDR, row_waits=None):
     return [ybase + 2 * q for q in range(16)] + [newhi + 2 * q for q in range(16)]
 
 
-def t_iw0(body, dmap, pairs, ybase, newhi, ad=NTT_ADDR):
-    """W1 (pairs=False) or W1' (pairs=True) -> W0, halves split by i (row stride 66).  The first half's 16 rows land
-    in registers no data occupies (ybase.. when free; the renamed pairs of REGROUP_DPP_SELECT may sit there)."""
-    ydst = [ybase + 2 * r for r in range(16)]
-    if any(d + o in range(ybase, ybase + 32) for d in dmap for o in (0, 1)):
-        free = [b + 2 * j for b in free_blocks_except(dmap) for j in range(4) if not newhi <= b < newhi + 32]
-        assert len(free) >= 16, free
-        ydst = free[:16]
+def t_iw0(body, dmap, ybase, newhi, ad):
+    """W1' -> W0 in the W1x layout, halves split by i (row stride 65); the first half's 16 rows land at ybase.."""
+    assert ad.w1x
     L = []
-    w1x = getattr(ad, "w1x", False)
-    rs = 65 if w1x else 66  # row stride (u64) of the W0 side
     for h in range(2):
-        if w1x:  # the half of blocks i < 16 (h = 0) is lanes 0-15 and 32-47
-            m = "0xffff" if h == 0 else "0xffff0000"
-            L += [f"s_mov_b32 exec_lo, {m}", f"s_mov_b32 exec_hi, {m}"]
-        else:
-            L += ([f"s_mov_b32 exec_lo, -1", f"s_mov_b32 exec_hi, 0"] if h == 0 else
-                  [f"s_mov_b32 exec_lo, 0", f"s_mov_b32 exec_hi, -1"])
+        L += exec_block_half(ad, h)
         for k in range(32):
-            if pairs:
-                if k < 16:
-                    L.append(f"ds_write_b64 {ad.t2wl}, {pv(dmap[k])} offset:{2 * k * 8}")
-                else:
-                    L.append(f"ds_write_b64 {ad.t2wh}, {pv(dmap[k])} offset:{2 * (k - 16) * 8}")
+            if k < 16:
+                L.append(f"ds_write_b64 {ad.t2wl}, {pv(dmap[k])} offset:{2 * k * 8}")
             else:
-                L.append(f"ds_write_b64 {ad.t4w}, {pv(dmap[k])} offset:{2 * k * 8}")
+                L.append(f"ds_write_b64 {ad.t2wh}, {pv(dmap[k])} offset:{2 * (k - 16) * 8}")
         L += EXEC_ALL
         if h == 1:
             L.append("s_waitcnt lgkmcnt(0)")
-        dst = ydst if h == 0 else [newhi + 2 * r for r in range(16)]
-        rb = ad.t2r if pairs else ad.t4r
+        dst = ybase if h == 0 else newhi
         for r in range(16):
-            L.append(f"ds_read_b64 {pv(dst[r])}, {rb} offset:{r * rs * 8}")
+            L.append(f"ds_read_b64 {pv(dst + 2 * r)}, {ad.t2r} offset:{r * 65 * 8}")
     L.append("s_waitcnt lgkmcnt(0)")
     body.raw(*L)
-    return ydst + [newhi + 2 * r for r in range(16)]
+    return [ybase + 2 * r for r in range(16)] + [newhi + 2 * r for r in range(16)]
 
 
-# The lane-pair regroup as two VOP2 selects per 32-bit word with a DPP partner-lane source (v_cndmask_b32_dpp, VCC set
-# by the SALU) instead of two DPP moves and two selects; the second slot's new value goes to a fresh register pair
-# (renamed in dmap) so neither select overwrites a value the partner lane still has to read.
-REGROUP_DPP_SELECT = False
-
-
-def regroup(sg, dmap, k, tmp, to_pairs, k2=None, w1x=False):
-    """W1 <-> W1' for register pair (k, k2 = k+16) of this lane and its partner (lane ^ 1).
-    to_pairs: even lane ends with (a_k, b_k), odd lane with (a_{k2}, b_{k2}).
-    back:     even lane ends with (a_k, a_{k2}), odd lane with (b_k, b_{k2}).
-    With REGROUP_DPP_SELECT the k2 slot moves to the pair tmp[0:2] (dmap updated) and the returned register base is
-    the one it left, free for the caller's next temporary; otherwise returns None."""
+def regroup(sg, dmap, k, tmp, k2=None, w1x=False):
+    """W1 -> W1' for register pair (k, k2 = k+16) of this lane and its partner (lane ^ 1, or lane ^ 32 with w1x):
+    the even lane ends with (a_k, b_k), the odd lane with (a_{k2}, b_{k2})."""
     kk2 = k + 16 if k2 is None else k2
     lo0, hi0, p0 = X(dmap, k)
     lo1, hi1, p1 = X(dmap, kk2)
     if w1x:
         # W1x (lane = i + 32 par): one half-wave exchange per word moves the lower lanes' x[k2] up and the upper
-        # lanes' x[k] down — the same permutation in both directions (it is an involution)
+        # lanes' x[k] down
         sg.add(f"v_permlane32_swap_b32 {lo0}, {lo1}", [lo0, lo1], [lo0, lo1], "dpp")
         sg.add(f"v_permlane32_swap_b32 {hi0}, {hi1}", [hi0, hi1], [hi0, hi1], "dpp")
-        return None
+        return
     T0, T1, U0, U1 = tmp
     par = f"s[{S_PAR}:{S_PAR + 1}]"
     dpp = "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-    if REGROUP_DPP_SELECT:
-        # both directions move the same values: the k2 slot of an even lane takes its partner's k slot, the k slot of an
-        # odd lane its partner's k2 slot (VOP2 select: D = VCC ? src1 : dpp(src0))
-        old = dmap[kk2]
-        sg.add(f"s_mov_b64 vcc, {par}", [par], ["vcc"], "salu")
-        sg.add(f"v_cndmask_b32_dpp {T0}, {lo0}, {lo1}, vcc {dpp}", [lo0, lo1, "vcc"], [T0], "dpp")
-        sg.add(f"v_cndmask_b32_dpp {T1}, {hi0}, {hi1}, vcc {dpp}", [hi0, hi1, "vcc"], [T1], "dpp")
-        sg.add(f"s_not_b64 vcc, {par}", [par], ["vcc", "scc"], "salu")
-        sg.add(f"v_cndmask_b32_dpp {lo0}, {lo1}, {lo0}, vcc {dpp}", [lo1, lo0, "vcc"], [lo0], "dpp")
-        sg.add(f"v_cndmask_b32_dpp {hi0}, {hi1}, {hi0}, vcc {dpp}", [hi1, hi0, "vcc"], [hi0], "dpp")
-        dmap[kk2] = int(T0[1:])
-        return old
-    if EXEC_MASK:
-        # both directions: T = partner's x[k], U = partner's x[k2] (four DPP moves, all lanes), then the odd lanes take
-        # x[k] <- U and the even lanes x[k2] <- T, each one EXEC-masked 64-bit move instead of two selects
-        sg.add(f"v_mov_b32_dpp {T0}, {lo0} {dpp}", [lo0], [T0], "dpp")
-        sg.add(f"v_mov_b32_dpp {T1}, {hi0} {dpp}", [hi0], [T1], "dpp")
-        sg.add(f"v_mov_b32_dpp {U0}, {lo1} {dpp}", [lo1], [U0], "dpp")
-        sg.add(f"v_mov_b32_dpp {U1}, {hi1} {dpp}", [hi1], [U1], "dpp")
-        mov64_masked(sg, par, p0, pair_of(U0, U1))
-        mov64_masked(sg, ("not", par), p1, pair_of(T0, T1))
-        return None
-    if to_pairs:
-        # T = partner x[k], U = partner x[k+16]; even: x[k+16] <- T ; odd: x[k] <- U
-        sg.add(f"v_mov_b32_dpp {T0}, {lo0} {dpp}", [lo0], [T0], "dpp")
-        sg.add(f"v_mov_b32_dpp {T1}, {hi0} {dpp}", [hi0], [T1], "dpp")
-        sg.add(f"v_mov_b32_dpp {U0}, {lo1} {dpp}", [lo1], [U0], "dpp")
-        sg.add(f"v_mov_b32_dpp {U1}, {hi1} {dpp}", [hi1], [U1], "dpp")
-        sg.add(f"v_cndmask_b32_e64 {lo0}, {lo0}, {U0}, {par}", [lo0, U0, par], [lo0])
-        sg.add(f"v_cndmask_b32_e64 {hi0}, {hi0}, {U1}, {par}", [hi0, U1, par], [hi0])
-        sg.add(f"v_cndmask_b32_e64 {lo1}, {T0}, {lo1}, {par}", [T0, lo1, par], [lo1])
-        sg.add(f"v_cndmask_b32_e64 {hi1}, {T1}, {hi1}, {par}", [T1, hi1, par], [hi1])
-    else:
-        # even holds (a_k, b_k) -> wants (a_k, a_{k+16}) ; odd holds (a_{k+16}, b_{k+16}) -> (b_k, b_{k+16})
-        sg.add(f"v_mov_b32_dpp {T0}, {lo0} {dpp}", [lo0], [T0], "dpp")   # partner's first
-        sg.add(f"v_mov_b32_dpp {T1}, {hi0} {dpp}", [hi0], [T1], "dpp")
-        sg.add(f"v_mov_b32_dpp {U0}, {lo1} {dpp}", [lo1], [U0], "dpp")   # partner's second
-        sg.add(f"v_mov_b32_dpp {U1}, {hi1} {dpp}", [hi1], [U1], "dpp")
-        # even: x[k+16] <- T (partner a_{k+16}) ; odd: x[k] <- U (partner b_k)
-        sg.add(f"v_cndmask_b32_e64 {lo1}, {T0}, {lo1}, {par}", [T0, lo1, par], [lo1])
-        sg.add(f"v_cndmask_b32_e64 {hi1}, {T1}, {hi1}, {par}", [T1, hi1, par], [hi1])
-        sg.add(f"v_cndmask_b32_e64 {lo0}, {lo0}, {U0}, {par}", [lo0, U0, par], [lo0])
-        sg.add(f"v_cndmask_b32_e64 {hi0}, {hi0}, {U1}, {par}", [hi0, U1, par], [hi0])
+    # T = partner x[k], U = partner x[k+16]; even: x[k+16] <- T ; odd: x[k] <- U
+    sg.add(f"v_mov_b32_dpp {T0}, {lo0} {dpp}", [lo0], [T0], "dpp")
+    sg.add(f"v_mov_b32_dpp {T1}, {hi0} {dpp}", [hi0], [T1], "dpp")
+    sg.add(f"v_mov_b32_dpp {U0}, {lo1} {dpp}", [lo1], [U0], "dpp")
+    sg.add(f"v_mov_b32_dpp {U1}, {hi1} {dpp}", [hi1], [U1], "dpp")
+    sg.add(f"v_cndmask_b32_e64 {lo0}, {lo0}, {U0}, {par}", [lo0, U0, par], [lo0])
+    sg.add(f"v_cndmask_b32_e64 {hi0}, {hi0}, {U1}, {par}", [hi0, U1, par], [hi0])
+    sg.add(f"v_cndmask_b32_e64 {lo1}, {T0}, {lo1}, {par}", [T0, lo1, par], [lo1])
+    sg.add(f"v_cndmask_b32_e64 {hi1}, {T1}, {hi1}, {par}", [T1, hi1, par], [hi1])
 
 
 def free_blocks_except(dmap, extra_busy=()):
@@ -1169,33 +788,6 @@ def tmul_lane(sg, S_even, S_odd, x, sl, tlo, thi, par3, amt):
     op_up = "v_add_u32" if e1 > e0 else "v_sub_u32"      # amount grows with the exponent
     op_dn = "v_sub_u32" if e1 > e0 else "v_add_u32"
     cls = shift_class(e0)
-    if EXEC_MASK:
-        tp = pair_of(tlo, thi)
-        if cls in (0, 1):
-            r0, w0 = (e0, 32 - e0) if cls == 0 else (e0 - 32, 64 - e0)
-            sg.add(f"{op_up} {A0}, {r0}, {par3}", [par3], [A0])
-            sg.add(f"{op_dn} {A1}, {w0}, {par3}", [par3], [A1])
-            sg.add(f"v_lshlrev_b64 {P[0]}, {A0}, {xp}", [A0, xp], [P[0]])
-            if cls == 0:
-                sg.add(f"v_bfe_u32 {v[4]}, {xhi}, {A1}, {A0}", [xhi, A1, A0], [v[4]])
-            else:
-                sg.add(f"v_lshrrev_b32 {v[4]}, {A1}, {xhi}", [A1, xhi], [v[4]])
-            sg.add(f"v_mad_u64_u32 {tp}, {c[0]}, {v[4]}, -1, {P[0]}", [v[4], P[0]], [tp, c[0]])
-            if cls == 1:
-                plus_eps_masked(sg, c[0], tp)
-                sg.add(f"v_lshlrev_b64 {P[3]}, 32, {tp}", [tp], [P[3]])
-                sg.add(f"v_mad_u64_u32 {tp}, {c[0]}, {thi}, -1, {P[3]}", [thi, P[3]], [tp, c[0]])
-            sg.add(f"v_mad_u64_u32 {P[0]}, {c[1]}, -1, 1, {tp}", [tp], [P[0], c[1]])
-            mov64_masked(sg, ("or", c[1], c[0]), tp, P[0])
-            return neg
-        sg.add(f"{op_dn} {A0}, {96 - e0}, {par3}", [par3], [A0])
-        sg.add(f"{op_up} {A1}, {e0 - 64}, {par3}", [par3], [A1])
-        sg.add(f"v_lshrrev_b64 {P[0]}, {A0}, {xp}", [A0, xp], [P[0]])
-        sg.add(f"v_lshlrev_b32 {v[4]}, {A1}, {xlo}", [A1, xlo], [v[4]])
-        sg.add(f"v_mad_u64_u32 {tp}, {JUNK}, {v[4]}, 1, {P[0]}", [v[4], P[0]], [tp, JUNK])
-        sg.add(f"v_sub_co_u32_e64 {thi}, {c[0]}, {thi}, {v[4]}", [thi, v[4]], [thi, c[0]])
-        minus_eps_masked(sg, c[0], tp)
-        return neg
     if cls == 0:
         # r = e, h = top r bits of x_hi (v_bfe: width 0 gives 0, so r = 0 needs no special case)
         sg.add(f"{op_up} {A0}, {e0}, {par3}", [par3], [A0])
@@ -1233,21 +825,19 @@ def tmul_lane(sg, S_even, S_odd, x, sl, tlo, thi, par3, amt):
     return neg
 
 
-def pair_stage_gmul_ks(tabs, fwd):
-    """Butterflies of the lane-pair stage that need a table twiddle (no common shift path)."""
-    E = tabs["CYC_FWD" if fwd else "CYC_INV"][5]
+def pair_stage_gmul_ks(tabs):
+    """Butterflies of the forward's lane-pair stage that need a table twiddle (no common shift path)."""
+    E = tabs["CYC_FWD"][5]
     return [k for k in range(16) if not lane_tmul_applies(E[k], E[k + 16])]
 
 
-def pair_stage(B, dmap, fwd, ad=NTT_ADDR, tabs=None, pre=None, busy=()):
-    """Cyclic stage q = 5 on lane pairs: regroup W1 -> W1' (DPP), then butterfly k of lane 2i + par uses
+def pair_stage(B, dmap, ad, tabs, pre=None, busy=()):
+    """The forward's cyclic stage q = 5 on lane pairs: regroup W1 -> W1', then butterfly k of lane 2i + par uses
     the twiddle w_g = 2^E[g], g = k + 16 par (E = the exponent row of the stage).  Where both lanes'
     exponents share one code path the multiply is a shift-twiddle tmul with per-lane shift amounts
     (tmul_lane); elsewhere a general multiply by the table value (entry g of the 32-entry table).
-    Forward: CT then canonical outputs (layout stays W1' for T2); inverse: GS then regroup back to W1."""
-    if tabs is None:
-        tabs = load_tables()
-    E = tabs["CYC_FWD" if fwd else "CYC_INV"][5]
+    CT, then canonical outputs (the layout stays W1' for T2)."""
+    E = tabs["CYC_FWD"][5]
     regs = []
     for b in free_blocks_except(dmap, busy):
         regs += list(range(b, b + 8))
@@ -1276,59 +866,31 @@ def pair_stage(B, dmap, fwd, ad=NTT_ADDR, tabs=None, pre=None, busy=()):
             wlo, whi = f"v{wb[2 * i]}", f"v{wb[2 * i] + 1}"
             if pre and k in pre:  # twiddle loaded earlier, latency hidden behind the previous stages
                 wlo, whi = f"v{pre[k]}", f"v{pre[k] + 1}"
-            freed = regroup(sg, dmap, k, tmp, True, w1x=getattr(ad, "w1x", False))
-            if freed is not None:
-                tmps[i % 2][0:2] = [freed, freed + 1]
+            regroup(sg, dmap, k, tmp, w1x=getattr(ad, "w1x", False))
             a, b = X(dmap, k), X(dmap, k + 16)
-            if fwd:
-                # last stage: canonical outputs from a canonical a (3 VALU) and a canonicalising add /
-                # borrow-fixed subtract (12 VALU per butterfly instead of 14 for add, sub and two canons)
-                canon(sg, sl, a)
-                if lane:
-                    neg = tmul_lane(sg, E[k], E[k + 16], b, sl, sl.v[2], sl.v[3], par3, (wlo, whi))
-                    ct_core_canon(sg, sl, a, b, neg)
-                else:
-                    # t = b * w into the slot's Z1 pair, then CT with t viewed as v2:v3
-                    gmul(sg, m, b, wlo, whi, m.v[8], m.v[9])
-                    ct_sl = Slot.__new__(Slot)
-                    ct_sl.v = [m.v[0], m.v[1], m.v[8], m.v[9], m.v[4], m.v[5], m.v[6], m.v[7]]
-                    ct_sl.P = [m.P[0], None, None, m.P[3]]
-                    ct_sl.c = sl.c
-                    ct_core_canon(sg, ct_sl, a, b, False)
+            # last stage: canonical outputs from a canonical a (3 VALU) and a canonicalising add /
+            # borrow-fixed subtract (12 VALU per butterfly instead of 14 for add, sub and two canons)
+            canon(sg, sl, a)
+            if lane:
+                neg = tmul_lane(sg, E[k], E[k + 16], b, sl, sl.v[2], sl.v[3], par3, (wlo, whi))
+                ct_core_canon(sg, sl, a, b, neg)
             else:
-                # inputs are canonical (loaded data), so either may be the subtrahend: a' = a + b and
-                # d = a - b, or d = b - a when the shift twiddle is negative (the product stays positive)
-                e0 = E[k] % 96
-                swap = lane and ((E[k] >= 96) != (e0 >= 64))
-                add_part1(sg, sl, a[0], a[1], b[0], b[1])
-                if swap:
-                    sub_seq(sg, sl, b[0], b[1], b[0], b[1], a[0], a[1])
-                else:
-                    sub_seq(sg, sl, b[0], b[1], a[0], a[1], b[0], b[1])
-                add_part2(sg, sl, a[2])
-                if lane:
-                    tmul_lane(sg, E[k], E[k + 16], b, sl, b[0], b[1], par3, (wlo, whi))
-                else:
-                    gmul(sg, m, b, wlo, whi, b[0], b[1])
-                freed = regroup(sg, dmap, k, [f"v{r}" for r in tmps[i % 2]], False, w1x=getattr(ad, "w1x", False))
-                if freed is not None:
-                    tmps[i % 2][0:2] = [freed, freed + 1]
+                # t = b * w into the slot's Z1 pair, then CT with t viewed as v2:v3
+                gmul(sg, m, b, wlo, whi, m.v[8], m.v[9])
+                ct_sl = Slot.__new__(Slot)
+                ct_sl.v = [m.v[0], m.v[1], m.v[8], m.v[9], m.v[4], m.v[5], m.v[6], m.v[7]]
+                ct_sl.P = [m.P[0], None, None, m.P[3]]
+                ct_sl.c = sl.c
+                ct_core_canon(sg, ct_sl, a, b, False)
         for j, op in enumerate(sg.ops):
             op.idx = j
         B.out(sg.schedule())
 
 
-def store_raw(dmap):
-    return store_rows(dmap, S_GB) + ["s_waitcnt vmcnt(0)"]
-
-
-def twist_rows(B, dmap, ad, bufs, ms, contiguous=True, regs=None, first_loaded=False, before_batch=None,
-               after_batch=None):
+def twist_rows(B, dmap, ad, bufs, ms, contiguous=True, regs=None, first_loaded=False):
     """x[r] *= table row r (general multiplies) for the 32 registers, in 4 batches of 8 rows; the next
     batch's 8 table rows are loaded into the other buffer before this batch multiplies, so the table
-    latency (L2 or LDS) hides behind the multiplies.  The slots' zero addend halves are set once.
-    before_batch / after_batch (bt): extra lines before / after batch bt's multiplies (the progressive one-pass
-    transposes: a wait for the rows an LDS read brings, the LDS writes of the rows just multiplied)."""
+    latency (L2 or LDS) hides behind the multiplies.  The slots' zero addend halves are set once."""
     B.raw(*[f"v_mov_b32 {m.v[z]}, 0" for m in ms for z in (9, 11)])
     buf = (lambda i, k: bufs[i] + 2 * k) if contiguous else (lambda i, k: regs[16 * i + 2 * k])
     if not first_loaded:
@@ -1338,16 +900,13 @@ def twist_rows(B, dmap, ad, bufs, ms, contiguous=True, regs=None, first_loaded=F
             B.raw(*[ad.tw_load(bt + 1, k, buf((bt + 1) % 2, k)) for k in range(8)], ad.tw_wait_n(8))
         else:
             B.raw(ad.tw_wait)
-        if before_batch:
-            B.raw(*before_batch(bt))
         B.mulrows(dmap, list(range(8 * bt, 8 * bt + 8)), [buf(bt % 2, k) for k in range(8)], ms, zero_hi=False)
-        if after_batch:
-            B.raw(*after_batch(bt))
 
 
-def fwd_core(B, tabs, dmap, ad=NTT_ADDR, stop=None, prefetch=False, first_stage=0):
+def fwd_core(B, tabs, dmap, ad, stop=None, prefetch=False, first_stage=0):
     """Forward transform of the W0 data in dmap (must be v64..v127); returns the output dmap (W0,
-    canonical).  With `stop`, returns early (debug bodies).  `prefetch` (the standalone kernel, whose
+    canonical).  stop="last": return after the lane-pair stage, the data in the W1' layout (the PBS bodies, which
+    run their MAC there).  `prefetch` (the standalone kernel, whose
     waves run in lockstep so a wait on a table load is not covered by other waves): the first twist
     batch is loaded before the G1 stages into v8..v23 and the lane-pair table twiddles right after T1,
     each load's latency hidden behind the stages in between (one or two fewer scratch slots there)."""
@@ -1359,77 +918,53 @@ def fwd_core(B, tabs, dmap, ad=NTT_ADDR, stop=None, prefetch=False, first_stage=
     g1_scales = [0] * 32
     for s in range(first_stage, 5):  # first_stage 1: the caller ran stage 0 (the PBS bodies' signed digits)
         gw = None
-        if s == 0 and PROGRESSIVE and prefetch:  # rows issued as pairs (k, k + 16), then the 8 twist-row loads
+        if s == 0 and prefetch:  # rows issued as pairs (k, k + 16), then the 8 twist-row loads
             gw = [f"s_waitcnt vmcnt({40 - 8 * (g + 1)})" for g in range(4)]
-        modes = plan["fwd_g1"]["modes"][16 * s:16 * s + 16] if plan else None
         B.tag = f"G1 stage {s}"
-        B.stage("ct", 16 >> s, tabs["G1_FWD"][s], dmap, fb, group_waits=gw, modes=modes,
-                scales=g1_scales if plan else None)
-    if plan:
-        assert g1_scales == [v % 192 for v in plan["fwd_g1"]["out_scales"]], "G1 scales differ from the plan's"
-    if stop == "g1":
-        return dmap
+        B.stage("ct", 16 >> s, tabs["G1_FWD"][s], dmap, fb, group_waits=gw,
+                modes=plan["fwd_g1"]["modes"][16 * s:16 * s + 16], scales=g1_scales)
+    assert g1_scales == [v % 192 for v in plan["fwd_g1"]["out_scales"]], "G1 scales differ from the plan's"
     # twist: 4 batches of 8 rows; table rows double-buffered in v8..v23 / v48..v63 (batch bt + 1
     # loads while batch bt multiplies), 2 multiply slots in v24..v47
-    prog = getattr(ad, "full_t", False) and PROGRESSIVE_FULL_T
-    after = (lambda bt: t1_full_writes(dmap, ad, range(8 * bt, 8 * bt + 8))) if prog else None
     B.tag = "twist"
-    twist_rows(B, dmap, ad, [8, 48], [MulSlot(24 + 12 * i, SG0 + 6 * i) for i in range(2)], first_loaded=prefetch,
-               after_batch=after)
-    if stop == "twist":
-        return dmap
+    twist_rows(B, dmap, ad, [8, 48], [MulSlot(24 + 12 * i, SG0 + 6 * i) for i in range(2)], first_loaded=prefetch)
     B.tag = "T1 transpose"
-    dmap = t1_full(B, dmap, ad, written=True) if prog else t1(B, dmap, 8, 64, ad)
-    if stop == "t1":
-        return dmap
+    dmap = t1(B, dmap, 8, 64, ad)
     pre, busy = None, ()
     if prefetch:
-        gks = pair_stage_gmul_ks(tabs, True)
+        gks = pair_stage_gmul_ks(tabs)
         fb0 = free_blocks_except(dmap)
         pre = {k: fb0[0] + 2 * i for i, k in enumerate(gks)}
         busy = tuple(range(fb0[0], fb0[0] + 8))
         B.raw(*[ad.lw_load(r, k) for k, r in pre.items()])
     fb = free_blocks_except(dmap, busy)
     cf = [True] * 32  # twist outputs are canonical
-    cyc_scales = list(plan["fwd_cyc"]["in_scales"]) if plan else None
+    cyc_scales = list(plan["fwd_cyc"]["in_scales"])
     for q in range(5):
         B.tag = f"cyclic stage {q}"
-        B.stage("ct", 16 >> q, tabs["CYC_FWD"][q], dmap, fb, cf, modes=plan["fwd_cyc"]["modes"][16 * q:16 * q + 16]
-                if plan else None, scales=cyc_scales)
-    if plan:
-        assert all(v % 192 == 0 for v in cyc_scales), "the cyclic blocks' outputs must be unscaled"
-    if stop == "cyc":
-        return dmap
+        B.stage("ct", 16 >> q, tabs["CYC_FWD"][q], dmap, fb, cf, modes=plan["fwd_cyc"]["modes"][16 * q:16 * q + 16],
+                scales=cyc_scales)
+    assert all(v % 192 == 0 for v in cyc_scales), "the cyclic blocks' outputs must be unscaled"
     B.tag = "lane-pair stage"
-    pair_stage(B, dmap, True, ad, tabs, pre, busy)
+    pair_stage(B, dmap, ad, tabs, pre, busy)
     if stop == "last":
         return dmap
     B.tag = "T2 transpose"
-    dmap = t_iw0(B, dmap, True, 96, 64, ad)
+    dmap = t_iw0(B, dmap, 96, 64, ad)
     B.tag = "store"
     return dmap
 
 
-def gen_fwd(tabs, stop=None):
+def gen_fwd(tabs):
     B = Body(tabs)
     dmap = [64 + 2 * r for r in range(32)]
     B.raw(f"s_mov_b64 s[{S_EXE}:{S_EXE + 1}], exec", f"s_mov_b32 s{S_X15}, 0x11111111")
     B.raw(*gen_bases("g", S_GB), *gen_bases("tw", S_TB))
-    ad = NTT_ADDR_W1X if FWD_W1X else NTT_ADDR
-    B.raw(*par_mask(ad))
-    if PROGRESSIVE and not stop:
-        rows = load_rows(dmap, S_GB)
-        B.raw(*[rows[r] for k in range(16) for r in (k, k + 16)])
-    else:
-        B.raw(*load_rows(dmap, S_GB), "s_waitcnt vmcnt(0)")
-    if FWD_STORE != "t2" and not stop:
-        dmap = fwd_core(B, tabs, dmap, ad, stop="last", prefetch=True)
-        B.raw(*direct_stores(dmap, FWD_STORE))
-        return B
-    dmap = fwd_core(B, tabs, dmap, ad, stop=stop, prefetch=True)
-    if stop:
-        B.raw(*store_raw(dmap))
-        return B
+    B.raw(*PAR_MASK)
+    # the first stage starts as the data rows arrive: rows issued as pairs (k, k + 16), waited in 4 groups
+    rows = load_rows(dmap, S_GB)
+    B.raw(*[rows[r] for k in range(16) for r in (k, k + 16)])
+    dmap = fwd_core(B, tabs, dmap, NTT_ADDR, prefetch=True)
     B.raw(*store_rows(dmap, S_GB))  # no final vmcnt wait: the wave may retire while its stores drain
     return B
 
@@ -1467,8 +1002,7 @@ def gen_fwd_ms64(tabs):
     B.raw(f"s_mov_b64 s[{S_EXE}:{S_EXE + 1}], exec", f"s_mov_b32 s{S_X15}, 0x11111111",
           f"s_mov_b32 s{S_H31}, 0x80000000")
     B.raw(*gen_bases("g", S_GB), *gen_bases("tw", S_TB), *gen_bases("o", S_OB))
-    ad = NTT_ADDR_W1X if FWD_W1X else NTT_ADDR
-    B.raw(*par_mask(ad))
+    B.raw(*PAR_MASK)
     B.raw(*load_rows(dmap, S_GB), "s_waitcnt vmcnt(0)")
     sg = Seg()
     sls = B.slots(free_blocks_except(dmap))
@@ -1477,55 +1011,9 @@ def gen_fwd_ms64(tabs):
     for i, op in enumerate(sg.ops):
         op.idx = i
     B.out(sg.schedule())
-    dmap = fwd_core(B, tabs, dmap, ad, prefetch=True)
+    dmap = fwd_core(B, tabs, dmap, NTT_ADDR, prefetch=True)
     B.raw(*store_rows(dmap, S_OB))
     return B
-
-
-def direct_stores(dmap, mode):
-    """After the lane-pair stage lane 2 i + par holds (x[k], x[k+16]) = outputs 64 i + 32 par + 2 k, + 1
-    (k < 16): store them straight from registers at %[pso] = 512 i + 256 par (bytes) + 16 k."""
-    out = []
-    if mode == "x2":
-        for k in range(16):
-            out.append(f"global_store_dwordx2 %[pso], {pv(dmap[k])}, s[{S_GB}:{S_GB + 1}] offset:{16 * k}")
-            out.append(f"global_store_dwordx2 %[pso], {pv(dmap[k + 16])}, s[{S_GB}:{S_GB + 1}] offset:{16 * k + 8}")
-        return out
-    busy = set()
-    for b in dmap:
-        busy.update((b, b + 1))
-    quads = [q for q in range(VLO, VHI, 4) if not any(r in busy for r in range(q, q + 4))]
-    assert len(quads) >= 4, quads
-    for k in range(16):
-        q = quads[k % len(quads)]
-        out.append(f"v_mov_b64 v[{q}:{q + 1}], {pv(dmap[k])}")
-        out.append(f"v_mov_b64 v[{q + 2}:{q + 3}], {pv(dmap[k + 16])}")
-        out.append(f"global_store_dwordx4 %[pso], v[{q}:{q + 3}], s[{S_GB}:{S_GB + 1}] offset:{16 * k}")
-    return out
-
-
-INV_PRE_LW = 40          # v40..v43: the inverse lane-pair table twiddles, loaded with the data
-INV_PRE_TW = 40          # v40..v55: the first untwist batch, loaded during the lane-pair stage
-
-
-def dit_exps(s):
-    """Exponents of DIT stage s = 1..5 of the inverse cyclic blocks (register distance 2^(s-1), storage
-    bit s of j = 2 reg + j0), indexed by the butterfly's first register r.
-
-    The inverse of the natural-in / bit-reversed-out cyclic DFT (omega = 8) is computed from its
-    bit-reversed input by decimation in time: stage s joins j and j + 2^s with the twiddle
-    w = omega^-(k 64 / 2^(s+1)), k = j mod 2^s, so CT butterflies need no canonical inputs (GS ones need a
-    canonical subtrahend).  k holds the lane bit j0, so the odd lanes' twiddle would differ from the even
-    lanes' by omega^-(64 / 2^(s+1)) at every stage; instead the odd lanes enter stage 1 scaled by the
-    product of those factors over the stages to come, sigma(j) = omega^-bitrev5(j >> 1), which the first
-    (lane-pair) stage applies as a GS butterfly with exactly the CYC_INV[5] twiddles (a scale common to a
-    butterfly's two inputs passes through it; the factor pending for bit s is used up at stage s, so the
-    outputs come out unscaled).  Every lane then uses the even-lane twiddle: k = 2 (r mod 2^(s-1))."""
-    d = 1 << (s - 1)
-    return [(-3 * (64 >> s) * (r % d)) % 192 for r in range(32)]
-
-
-INV_W1PP = True  # standalone inverse: cyclic blocks in the W1'' layout (t1_w1pp / dit_exps_pp / pair_stage_dit)
 
 
 def inv_last_exp(r):
@@ -1539,7 +1027,7 @@ def dit_exps_pp(s):
     return [(-3 * (32 >> s) * (r % (1 << s))) % 192 for r in range(32)]
 
 
-def t1_w1pp(body, dmap, dst, ad=NTT_ADDR):
+def t1_w1pp(body, dmap, dst, ad):
     """W0 (lane = j, register = block i) -> W1'' (lane = 2 i + j5, register r = j & 31) through LDS, halves split
     by i: every lane writes rows i = 16 h .. 16 h + 15 at (i & 15) 66 + j + (j >> 5) (%[t1x]); lanes 32 h .. 32 h + 31
     (blocks 16 h ..) read their 32 values at (i & 15) 66 + 33 j5 + r (%[t1y]).  Rows 16.. stay live in half 0, so
@@ -1558,26 +1046,16 @@ def t1_w1pp(body, dmap, dst, ad=NTT_ADDR):
     return list(dst)
 
 
-def t_w1pp_w0_full_writes(dmap, ad, regs):
-    return [f"ds_write_b64 {ad.tfb}, {pv(dmap[R])} offset:{(2 * (R >> 1) + 32 * (R & 1)) * 8}" for R in regs]
-
-
-# waits of the untwist batches on the progressive W1'' -> W0 reads (LDS completes in order; lgkmcnt saturates at 15):
-# batch bt multiplies rows 8 bt .. 8 bt + 7
-UNTWIST_ROW_WAITS = ["s_waitcnt lgkmcnt(15)", "s_waitcnt lgkmcnt(15)", "s_waitcnt lgkmcnt(8)", "s_waitcnt lgkmcnt(0)"]
-
-
-def t_w1pp_w0(body, dmap, ybase, newhi, ad=NTT_ADDR, written=False, reads_pending=False):
+def t_w1pp_w0(body, dmap, ybase, newhi, ad):
     """After pair_stage_dit lane 2 i + par holds output n = 2 m + par + 32 q in register 2 m + q: -> W0 through
     LDS, halves split by i (rows (i & 15) 66, columns n + (n >> 5)); reads at %[t1x] + 66 rho.  ad.full_t: one pass
     through the 32 x 66 tile of t1_full (writes at %[tfb] + 2 m + 32 q, reads at %[tfw] + 66 i), the rows landing in
     the registers of dmap."""
     if getattr(ad, "full_t", False):
-        L = [] if written else t_w1pp_w0_full_writes(dmap, ad, range(32))
+        L = [f"ds_write_b64 {ad.tfb}, {pv(dmap[R])} offset:{(2 * (R >> 1) + 32 * (R & 1)) * 8}" for R in range(32)]
         L.append("s_waitcnt lgkmcnt(0)")
         L += [f"ds_read_b64 {pv(dmap[i])}, {ad.tfw} offset:{i * FULL_STRIDE * 8}" for i in range(32)]
-        if not reads_pending:
-            L.append("s_waitcnt lgkmcnt(0)")
+        L.append("s_waitcnt lgkmcnt(0)")
         body.raw(*L)
         return list(dmap)
     L = []
@@ -1601,7 +1079,7 @@ def pair_stage_dit_gmul_ms():
     return [m for m in range(16) if not lane_tmul_applies(inv_last_exp(2 * m), inv_last_exp(2 * m + 1))]
 
 
-def pair_stage_dit(B, dmap, ad, pre, busy, after_half=None):
+def pair_stage_dit(B, dmap, ad, pre, busy):
     """Last DIT stage of the inverse cyclic blocks in W1'': j and j + 32 sit in the two lanes of a pair (register
     r = j & 31).  Regroup registers (2 m, 2 m + 1) across the pair (even lane: elements 2 m, 2 m + 32; odd lane:
     2 m + 1, 2 m + 33), then a CT butterfly whose twiddle exponent differs by 3 between the lanes (tmul_lane), or
@@ -1626,9 +1104,7 @@ def pair_stage_dit(B, dmap, ad, pre, busy, after_half=None):
             mm = msl[i % 2]
             sl = slot_view(mm, c23[i % 2])
             Se, So = inv_last_exp(2 * m), inv_last_exp(2 * m + 1)
-            freed = regroup(sg, dmap, 2 * m, tmp, True, k2=2 * m + 1, w1x=getattr(ad, "w1x", False))
-            if freed is not None:
-                tmps[i % 2][0:2] = [freed, freed + 1]
+            regroup(sg, dmap, 2 * m, tmp, k2=2 * m + 1, w1x=getattr(ad, "w1x", False))
             a, b = X(dmap, 2 * m), X(dmap, 2 * m + 1)
             if lane_tmul_applies(Se, So):
                 neg = tmul_lane(sg, Se, So, b, sl, sl.v[2], sl.v[3], par3, tuple(f"v{r}" for r in amts[i % 2]))
@@ -1643,8 +1119,6 @@ def pair_stage_dit(B, dmap, ad, pre, busy, after_half=None):
         for j, op in enumerate(sg.ops):
             op.idx = j
         B.out(sg.schedule())
-        if after_half:
-            B.raw(*after_half(half))
 
 
 def w1p_as_w1pp(dmap):
@@ -1655,18 +1129,18 @@ def w1p_as_w1pp(dmap):
     return [dmap[(r >> 1) + 16 * (r & 1)] for r in range(32)]
 
 
-def inv_cyc_w1pp(B, dmap, ad, dst=None, pre_base=72, ybase=96, newhi=64, w1p_in=False):
-    """W0 data -> T1'' -> DIT stages 0..4 in registers -> the lane-pair DIT stage -> W0.  The lane-pair stage's
-    table twiddles load right after T1'' (into pre_base..), five stages ahead of their use.  Register plan
-    (standalone defaults; the PBS bodies pass their own): `dst` (32 pairs) may reuse only rows 0..15 of `dmap`,
-    pre_base.. (8 registers) must be free of `dst`, and `ybase` (the first output half) must be free of `dst`.
+def inv_cyc_w1pp(B, dmap, ad, pre_base=72, ybase=96, newhi=64, w1p_in=False):
+    """W0 data -> T1'' (into v8..v71) -> DIT stages 0..4 in registers -> the lane-pair DIT stage -> W0.  The lane-pair
+    stage's table twiddles load right after T1'' (into pre_base..), five stages ahead of their use.  Register plan
+    (standalone defaults; the PBS bodies pass their own): pre_base.. (8 registers) and `ybase` (the first output half)
+    must be free of the transposed data.
     w1p_in: `dmap` already holds the data in the forward's W1' layout (no T1'', see w1p_as_w1pp)."""
     if w1p_in:
         dmap = w1p_as_w1pp(dmap)
     else:
         assert not getattr(ad, "full_t", False)
         B.tag = "T1'' transpose"
-        dmap = t1_w1pp(B, dmap, dst or [8 + 2 * r for r in range(32)], ad)
+        dmap = t1_w1pp(B, dmap, [8 + 2 * r for r in range(32)], ad)
     ms = pair_stage_dit_gmul_ms()
     pre = {m: pre_base + 2 * i for i, m in enumerate(ms)}
     assert len(ms) <= 4
@@ -1678,58 +1152,26 @@ def inv_cyc_w1pp(B, dmap, ad, dst=None, pre_base=72, ybase=96, newhi=64, w1p_in=
     for s in range(5):
         B.tag = f"cyclic stage {s}"
         B.stage("ct", 1 << s, dit_exps_pp(s), dmap, fb, cf, by_reg=True)
-    prog = getattr(ad, "full_t", False) and PROGRESSIVE_FULL_T
-    after = (lambda h: t_w1pp_w0_full_writes(dmap, ad, range(16 * h, 16 * h + 16))) if prog else None
     B.tag = "lane-pair stage"
-    pair_stage_dit(B, dmap, ad, pre, busy, after_half=after)
+    pair_stage_dit(B, dmap, ad, pre, busy)
     assert getattr(ad, "full_t", False) or not set(range(ybase, ybase + 32)) & {r for b in dmap for r in (b, b + 1)}
     B.tag = "T2'' transpose"
-    return t_w1pp_w0(B, dmap, ybase, newhi, ad, written=prog, reads_pending=prog)
+    return t_w1pp_w0(B, dmap, ybase, newhi, ad)
 
 
-def inv_core(B, tabs, dmap, ad=NTT_ADDR, prefetch=False, row_waits=None, w1pp=False, w1pp_regs=None, g1_busy=(),
-             before_g1=()):
-    """Inverse transform of the W0 data in dmap; returns the output dmap (W0, canonical).  g1_busy / before_g1: registers
-    the G1 stages leave alone and lines emitted right before them (the external-product bodies' out-row loads).  `prefetch`
-    (standalone kernel, see fwd_core): the caller has loaded the lane-pair table twiddles into
-    v40..v43 with the data; the first untwist batch is loaded into v40..v55 after the lane-pair stage
-    and stays there through the cyclic stages and T4 (the one register range free in both layouts)."""
-    if w1pp:
-        dmap = inv_cyc_w1pp(B, dmap, ad, **(w1pp_regs or {}))
-        prefetch, busy = False, ()
-    else:
-        dmap = t1(B, dmap, 8, 64, ad, row_waits)
-        gks = pair_stage_gmul_ks(tabs, False)
-        pre = {k: INV_PRE_LW + 2 * i for i, k in enumerate(gks)} if prefetch else None
-        pair_stage(B, dmap, False, ad, tabs, pre, tuple(range(INV_PRE_LW, INV_PRE_LW + 8)) if prefetch else ())
-        busy = tuple(range(INV_PRE_TW, INV_PRE_TW + 16)) if prefetch else ()
-        if prefetch:
-            B.raw(*[ad.tw_load(0, k, INV_PRE_TW + 2 * k) for k in range(8)])
-        fb = free_blocks_except(dmap, busy)
-        cf = [False] * 32
-        if INV_CYC_DIT:
-            for s in range(1, 6):
-                B.stage("ct", 1 << (s - 1), dit_exps(s), dmap, fb, cf, by_reg=True)
-        else:  # r2 form (GS, canonical subtrahends), kept for tools/variant_probe A/B runs
-            for q in range(4, -1, -1):
-                B.stage("gs", 16 >> q, tabs["CYC_INV"][q], dmap, fb, cf)
-        dmap = t_iw0(B, dmap, False, 96, 64, ad)
+def inv_core(B, tabs, dmap, ad, w1pp_regs=None, g1_busy=(), before_g1=()):
+    """Inverse transform of the W0 data in dmap; returns the output dmap (W0, canonical).  The cyclic blocks run in the
+    W1'' layout (inv_cyc_w1pp, whose register plan w1pp_regs overrides).  g1_busy / before_g1: registers the G1 stages
+    leave alone and lines emitted right before them (the external-product bodies' out-row loads)."""
+    dmap = inv_cyc_w1pp(B, dmap, ad, **(w1pp_regs or {}))
     # untwist: table rows and multiply slots in the registers the data does not occupy
     B.tag = "untwist"
-    free = free_blocks_except(dmap, busy)
     regs = []
-    for b in free:
+    for b in free_blocks_except(dmap):
         regs += list(range(b, b + 8))
-    if prefetch:
-        assert len(regs) >= 40, len(regs)
-        tregs = list(range(INV_PRE_TW, INV_PRE_TW + 16)) + regs[0:16]
-        ms = [MulSlot(0, SG0, regs[16:28]), MulSlot(0, SG0 + 6, regs[28:40])]
-        twist_rows(B, dmap, ad, None, ms, contiguous=False, regs=tregs, first_loaded=True)
-    else:
-        assert len(regs) >= 56, len(regs)
-        prog = w1pp and getattr(ad, "full_t", False) and PROGRESSIVE_FULL_T  # the W1'' -> W0 reads are still landing
-        twist_rows(B, dmap, ad, [regs[0], regs[16]], [MulSlot(0, SG0 + 6 * i, regs[32 + 12 * i:44 + 12 * i]) for i in range(2)],
-                   contiguous=False, regs=regs, before_batch=(lambda bt: [UNTWIST_ROW_WAITS[bt]]) if prog else None)
+    assert len(regs) >= 56, len(regs)
+    twist_rows(B, dmap, ad, [regs[0], regs[16]], [MulSlot(0, SG0 + 6 * i, regs[32 + 12 * i:44 + 12 * i]) for i in range(2)],
+               contiguous=False, regs=regs)
     B.raw(*before_g1)
     fb = free_blocks_except(dmap, tuple(g1_busy))
     cf = [True] * 32  # untwist outputs are canonical
@@ -1747,27 +1189,15 @@ def inv_core(B, tabs, dmap, ad=NTT_ADDR, prefetch=False, row_waits=None, w1pp=Fa
     return dmap
 
 
-def gen_inv(tabs, stop=None):
+def gen_inv(tabs):
     B = Body(tabs)
     dmap = [64 + 2 * r for r in range(32)]
     B.raw(f"s_mov_b64 s[{S_EXE}:{S_EXE + 1}], exec", f"s_mov_b32 s{S_X15}, 0x11111111")
     B.raw(*gen_bases("g", S_GB), *gen_bases("tw", S_TB))
-    ad = NTT_ADDR_W1X if INV_W1X and INV_W1PP else NTT_ADDR
-    B.raw(*par_mask(ad))
-    if INV_W1PP:
-        B.raw(*load_rows(dmap, S_GB), "s_waitcnt vmcnt(0)")
-        dmap = inv_core(B, tabs, dmap, ad, w1pp=True)
-        B.raw(*store_rows(dmap, S_GB))
-        return B
-    gks = pair_stage_gmul_ks(tabs, False)
-    B.raw(*load_rows(dmap, S_GB), *[NTT_ADDR.lw_load(INV_PRE_LW + 2 * i, k) for i, k in enumerate(gks)])
-    rw = None
-    if PROGRESSIVE_INV:  # row r is written to LDS once it has landed (the pair twiddles are waited for later)
-        rw = [f"s_waitcnt vmcnt({32 + len(gks) - 1 - r})" for r in range(32)]
-    else:
-        B.raw("s_waitcnt vmcnt(0)")
-    dmap = inv_core(B, tabs, dmap, prefetch=True, row_waits=rw)
-    B.raw(*store_rows(dmap, S_GB))  # no final vmcnt wait: the wave may retire while its stores drain
+    B.raw(*PAR_MASK)
+    B.raw(*load_rows(dmap, S_GB), "s_waitcnt vmcnt(0)")
+    dmap = inv_core(B, tabs, dmap, NTT_ADDR)
+    B.raw(*store_rows(dmap, S_GB))
     return B
 
 
@@ -1842,15 +1272,11 @@ def mac_row(sg, L, bufs_of_terms, slot, out):
     sg.add(f"v_cndmask_b32_e64 v{out + 1}, v{out + 1}, {a0h}, {f[9]}", [f"v{out + 1}", a0h, f[9]], [f"v{out + 1}"])
 
 
-def mac_phase(B, L, dmap, vhi=MAC_VHI, bufs=None, after_row=None):
+def mac_phase(B, L, dmap, vhi=MAC_VHI):
     """Rows 0..31 of y = sum_q d_q G_q into dmap (W0: lane j of row r = element 64 r + j of the block).  Term (r, q)
-    loads d_q row r from %[d] + q %[dstep] and G_q row r from %[gg] + q %[gstep] (bytes).  bufs / after_row (the
-    wave-specialised producer): another term ring, and lines emitted after each row (its hand-off write)."""
+    loads d_q row r from %[d] + q %[dstep] and G_q row r from %[gg] + q %[gstep] (bytes)."""
     assert 2 <= L <= 8 and S_MB + 4 * L <= 96
-    if bufs is None:
-        bufs, slot = mac_ring(vhi)
-    else:
-        slot = mac_ring(vhi)[1]
+    bufs, slot = mac_ring(vhi)
     ring = len(bufs)
     dq = lambda q: S_MB + 2 * q
     gq = lambda q: S_MB + 2 * L + 2 * q
@@ -1888,8 +1314,6 @@ def mac_phase(B, L, dmap, vhi=MAC_VHI, bufs=None, after_row=None):
         nxt = min(issued + L, total)
         B.raw(*[l for t in range(issued, nxt) for l in issue(t)])
         issued = nxt
-        if after_row:
-            B.raw(*after_row(r))
 
 
 def gen_inv_mac(tabs, L, vhi=MAC_VHI):
@@ -1898,30 +1322,15 @@ def gen_inv_mac(tabs, L, vhi=MAC_VHI):
     B.raw(f"s_mov_b64 s[{S_EXE}:{S_EXE + 1}], exec", f"s_mov_b32 s{S_X15}, 0x11111111")
     mac_phase(B, L, dmap, vhi)
     B.raw(*gen_bases("g", S_GB), *gen_bases("tw", S_TB))
-    ad = NTT_ADDR_W1X if INV_W1X else NTT_ADDR
-    B.raw(*par_mask(ad))
-    assert INV_W1PP
-    dmap = inv_core(B, tabs, dmap, ad, w1pp=True)
+    B.raw(*PAR_MASK)
+    dmap = inv_core(B, tabs, dmap, NTT_ADDR)
     B.raw(*store_rows(dmap, S_GB))
     return B
 
 
-# The wave-specialised form (r5 probe, not emitted into the library: measured 2-5 % slower than the fused kernel): a two-wave workgroup loops over units; its producer wave
-# forms unit u's block of y (mac_phase) while its consumer wave runs the inverse of unit u - 1, so the MAC's memory
-# phase and the inverse's issue phase overlap inside every SIMD (the dispatcher puts two producers and two consumers on
-# each SIMD, tools/placement_probe.hip) instead of running in lockstep across the device.  Hand-off through the
-# workgroup's 16 KiB LDS buffer (row r, lane j at %[yw] + 512 r, %[yw] = buffer + 8 lane); the consumer's transposes
-# use a second region.  Per unit both waves execute two s_barriers: (1) the rows are written, (2) the consumer has read
-# them (the producer writes the next unit's rows only after it).
-WS_LS = (4, 6)   # l (k + 1) of the 3_3 and 4_4 shapes (k = 1, l = 2 / 3); other L keep ntt_tw_inv_mac_kernel
-
-
-WS_OUT = (124, 126)   # the producer's row results alternate between these pairs (each row's hand-off write reads one)
-
-
 def emit(name, body, ops_in, sgpr_extra=(), vhi=None):
     clob = ([f'"v{i}"' for i in range(VLO, vhi or VHI)] + [f'"s{i}"' for i in list(SGPR_CLOBBER) + list(sgpr_extra)] +
-            ['"scc"', '"memory"'] + (['"vcc"'] if REGROUP_DPP_SELECT else []))
+            ['"scc"', '"memory"'])
     text = "\n".join(f'      "{l}\\n"' for l in body.lines)
     return (f"// {name}: {body.nvalu} VALU, {len(body.lines)} lines\n"
             f"#define MI_TW_BODY_{name.upper()}(...) asm volatile(\\\n" +

@@ -28,16 +28,16 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gen_tw_kernel as T  # noqa: E402
-from gen_tw_kernel import (JUNK, MS_SGPRS, S_EXE, S_GB, S_H31, S_OB, S_PAR, S_TB, S_X15, Body, Seg, X,  # noqa: E402
-                           emit, free_blocks_except, fwd_core, gen_bases, inv_core, load_rows, minus_eps,
+from gen_tw_kernel import (JUNK, MS_SGPRS, NTT_ADDR, PAR_MASK, S_EXE, S_GB, S_H31, S_OB, S_TB, S_X15,  # noqa: E402
+                           Body, Seg, X, emit, free_blocks_except, fwd_core, gen_bases, inv_core, load_rows, minus_eps,
                            modswitch_native, pv, store_rows)
 
 
-def _prologue(B, ad, extra=()):
+def _prologue(B):
     B.raw(f"s_mov_b64 s[{S_EXE}:{S_EXE + 1}], exec", f"s_mov_b32 s{S_X15}, 0x11111111",
-          f"s_mov_b32 s{S_H31}, 0x80000000", *extra)
+          f"s_mov_b32 s{S_H31}, 0x80000000")
     B.raw(*gen_bases("g", S_GB), *gen_bases("tw", S_TB), *gen_bases("o", S_OB))
-    B.raw(*T.par_mask(ad))
+    B.raw(*PAR_MASK)
 
 
 def _sched(B, sg):
@@ -67,9 +67,8 @@ def gen_fwd_view(tabs, kind):
     """Standard rows (%[g_*]) -> conversion -> forward transform -> NTT rows (%[o_*])."""
     B = Body(tabs)
     dmap = [64 + 2 * r for r in range(32)]
-    ad = T.NTT_ADDR_W1X if T.FWD_W1X else T.NTT_ADDR
-    _prologue(B, ad)
-    if kind == "copy" and T.PROGRESSIVE:  # as gen_fwd: stage 0 starts as the row pairs (k, k + 16) land
+    _prologue(B)
+    if kind == "copy":  # as gen_fwd: stage 0 starts as the row pairs (k, k + 16) land
         rows = load_rows(dmap, S_GB)
         B.raw(*[rows[r] for k in range(16) for r in (k, k + 16)])
     else:
@@ -80,7 +79,7 @@ def gen_fwd_view(tabs, kind):
         for r in range(32):
             (conv_pow2 if kind == "pow2" else conv_decomp)(sg, sls[r % len(sls)], X(dmap, r))
         _sched(B, sg)
-    dmap = fwd_core(B, tabs, dmap, ad, prefetch=True)
+    dmap = fwd_core(B, tabs, dmap, NTT_ADDR, prefetch=True)
     B.raw(*store_rows(dmap, S_OB))  # no final vmcnt wait: the wave may retire while its stores drain
     return B
 
@@ -141,10 +140,9 @@ def gen_inv_view(tabs, kind):
     standard rows (%[o_*])."""
     B = Body(tabs)
     dmap = [64 + 2 * r for r in range(32)]
-    ad = T.NTT_ADDR_W1X if T.INV_W1X else T.NTT_ADDR
-    _prologue(B, ad)
+    _prologue(B)
     B.raw(*load_rows(dmap, S_GB), "s_waitcnt vmcnt(0)")
-    dmap = inv_core(B, tabs, dmap, ad, w1pp=True)
+    dmap = inv_core(B, tabs, dmap, NTT_ADDR)
     busy = {r for b in dmap for r in (b, b + 1)}
     assert not busy & set(range(8, 64)), "the epilogue expects the inverse's output in v64..v127"
     slots = B.slots(list(EPI_SLOTS))

@@ -33,7 +33,7 @@ SALU = 1.5  # measured issue cost of an SALU instruction among the bodies' VALU 
 
 
 def align_cost(m, t_canon):
-    """Issue cycles of t = 2^m x, canonical (gen_tw_kernel.tmul / the ALIAS_COPY path for +-1)."""
+    """Issue cycles of t = 2^m x, canonical (gen_tw_kernel.tmul / ct_core's copy of a +-1 operand)."""
     e = m % 96
     if e == 0:
         return 4.72 if t_canon else 13.2

@@ -49,8 +49,7 @@ def blocks_table():
     import gen_tw_kernel as T
     tabs = T.load_tables()
     out = ["# Per-block VALU of the N = 2048 twisted transform bodies (tools/valu_cost.py --blocks)", "",
-           f"W1x layout: forward {T.FWD_W1X}, inverse {T.INV_W1X}.  VALU = wave instructions, cycles = the issue model "
-           "(tools/valu_probe.hip costs).  Butterfly rows: VALU of one butterfly as generated (before scheduling; "
+           "VALU = wave instructions, cycles = the issue model (tools/valu_probe.hip costs).  Butterfly rows: VALU of one butterfly as generated (before scheduling; "
            "canonicalisation folded into the stage that needs it).", ""]
     for name, body in (("forward", T.gen_fwd(tabs)), ("inverse", T.gen_inv(tabs))):
         out += [f"## {name}: {body.nvalu} VALU, {cycles(body.lines)[0]:.0f} cycles", "",

@@ -1,9 +1,14 @@
-// variant_probe.hip — diagnostic build (not part of the library): times the generated variants of the
-// twisted N = 2048 transform body (tools/gen_variants.py -> tools/_variant_bodies.hpp) against each other
-// on one stream, interleaved in rounds so a clock drift hits every variant alike, and checks that every
-// variant writes the same bits as variant 0.
+// variant_probe.hip — diagnostic build (not part of the library): times the forward and inverse bodies of the twisted
+// N = 2048 transform that several trees generate (tools/gen_variants.py TOOLS_DIR... -> tools/_variant_bodies.hpp; the
+// default is this tree twice, a body and its identical control) against each other on one stream, interleaved in
+// rounds so a clock drift hits every variant alike, and reports per variant whether it writes the same bits as
+// variant 0.  One more variant past the generated ones is body 0 in the library's launch form (forward: one wave per
+// workgroup, inverse: four).
 //
-//   python tools/gen_variants.py > tools/_variant_bodies.hpp
+// The probe passes every body the library's per-lane addresses (the W1x lane map, lane = i + 32 par, as
+// ntt64_tw_device.hpp).  A tree whose bodies need other per-lane addresses is out of its scope.
+//
+//   python tools/gen_variants.py [TOOLS_DIR ...] > tools/_variant_bodies.hpp
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/variant_probe.hip -o tools/variant_probe
 //   ./tools/variant_probe [batch]          (one JSON line per variant)
 #include <hip/hip_runtime.h>
@@ -22,69 +27,47 @@ static constexpr int WAVE_LDS2 = 1088;
 
 #define FWD_ARGS                                                                                              \
   [g_lo] "s"(glo), [g_hi] "s"(ghi), [tw_lo] "s"(twlo), [tw_hi] "s"(twhi), [lw] "s"(lw), [l8] "v"(l8),          \
-      [t1w] "v"(t1w), [t1r] "v"(t1r), [t2wl] "v"(t2wl), [t2wh] "v"(t2wh), [t2r] "v"(t2r), [lwo] "v"(lwo),        \
-      [pso] "v"(pso)
+      [t1w] "v"(t1w), [t1r] "v"(t1r), [t2wl] "v"(t2wl), [t2wh] "v"(t2wh), [t2r] "v"(t2r), [lwo] "v"(lwo)
 #define INV_ARGS                                                                                              \
   [g_lo] "s"(glo), [g_hi] "s"(ghi), [tw_lo] "s"(twlo), [tw_hi] "s"(twhi), [lw] "s"(lw), [l8] "v"(l8),          \
       [t1w] "v"(t1w), [t1r] "v"(t1r), [t4w] "v"(t4w), [t4r] "v"(t4r), [lwo] "v"(lwo), [t1x] "v"(t1x),        \
       [t1y] "v"(t1y)
 
-// STAG > 0 (r6 stagger probe): the first generation's waves start in four slots of 1,024 (wave index >> 10), slot s
-// sleeping s x STAG x 64 cycles before its row loads, so the first slot's rows arrive at the full HBM rate instead
-// of every resident wave's rows arriving together
-template <int V, bool FWD, int W = 4, int STAG = 0>
+template <int V, bool FWD, int W>
 __global__ __launch_bounds__(64 * W) void probe_kernel(u64* __restrict__ data, uint32_t batch, const u64* __restrict__ twist) {
   __shared__ u64 lds[W * WAVE_LDS2];
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t poly = blockIdx.x * W + wv;
   if (poly >= batch) return;
-  if constexpr (STAG > 0) {
-    const uint32_t slot = poly < 4096 ? poly >> 10 : 0;
-    for (uint32_t k = 0; k < slot; ++k) {
-      if constexpr (STAG > 127) {
-        __builtin_amdgcn_s_sleep(127);
-        __builtin_amdgcn_s_sleep(STAG - 127);
-      } else {
-        __builtin_amdgcn_s_sleep(STAG);
-      }
-    }
-  }
   u64* p = data + (uint64_t)poly * 2048;
   const uint32_t S = (uint32_t)(uintptr_t)(lds + wv * WAVE_LDS2);
-  constexpr int W1X[] = MI_VARIANT_W1X;
-  // the lane pair: lanes 2i, 2i + 1 (W1 / W1'') or i, i + 32 (W1x, r6)
-  const bool x = W1X[V];
-  const uint32_t par = x ? lane >> 5 : lane & 1, i = x ? lane & 31 : lane >> 1;
+  // the lane pair of block i: lanes i and i + 32
+  const uint32_t par = lane >> 5, i = lane & 31;
   const uint32_t l8 = lane * 8;
   const uint32_t t1w = S + (lane & 31) * 8;
-  const uint32_t t1r = S + (i * (x ? 33 : 34) + par) * 8;
+  const uint32_t t1r = S + (i * 33 + par) * 8;
   const uint32_t lwo = par * 128;
   const uint32_t glo = (uint32_t)(uintptr_t)p, ghi = (uint32_t)((uintptr_t)p >> 32);
   const uint32_t twlo = (uint32_t)(uintptr_t)twist, twhi = (uint32_t)((uintptr_t)twist >> 32);
   const u64* lw = twist + 2048;
   if constexpr (FWD) {
-    const uint32_t rs = x ? 65 : 66;
-    const uint32_t t2wl = S + ((i & 15) * rs + 33 * par) * 8;
-    const uint32_t t2wh = S + ((i & 15) * rs + 31 * par + 1) * 8;
+    const uint32_t t2wl = S + ((i & 15) * 65 + 33 * par) * 8;
+    const uint32_t t2wh = S + ((i & 15) * 65 + 31 * par + 1) * 8;
     const uint32_t t2r = S + (lane ^ (lane >> 5)) * 8;
-    const uint32_t pso = i * 512 + par * 256;
-    if constexpr (V == 0) MI_TW_BODY_FWD_V0(FWD_ARGS);
-    if constexpr (V == 1) MI_TW_BODY_FWD_V1(FWD_ARGS);
-    if constexpr (V == 2) MI_TW_BODY_FWD_V2(FWD_ARGS);
-    if constexpr (V == 3) MI_TW_BODY_FWD_V3(FWD_ARGS);
+#define MI_RUN_FWD(n) \
+  if constexpr (V == n) MI_TW_BODY_FWD_V##n(FWD_ARGS);
+    MI_FOR_EACH_VARIANT(MI_RUN_FWD)
   } else {
-    const uint32_t t4w = S + ((i & 15) * (x ? 65 : 66) + par) * 8;
+    const uint32_t t4w = S + ((i & 15) * 65 + par) * 8;
     const uint32_t t4r = S + lane * 8;
     const uint32_t t1x = S + (lane + (lane >> 5)) * 8;
     const uint32_t t1y = S + ((i & 15) * 66 + 33 * par) * 8;
-    if constexpr (V == 0) MI_TW_BODY_INV_V0(INV_ARGS);
-    if constexpr (V == 1) MI_TW_BODY_INV_V1(INV_ARGS);
-    if constexpr (V == 2) MI_TW_BODY_INV_V2(INV_ARGS);
-    if constexpr (V == 3) MI_TW_BODY_INV_V3(INV_ARGS);
+#define MI_RUN_INV(n) \
+  if constexpr (V == n) MI_TW_BODY_INV_V##n(INV_ARGS);
+    MI_FOR_EACH_VARIANT(MI_RUN_INV)
   }
 }
-static_assert(MI_N_VARIANTS == 4, "probe_kernel dispatches 4 variants");
 
 __global__ void fill(u64* d, size_t n, u64 seed) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -114,37 +97,23 @@ static void launch(bool fwd, u64* data, uint32_t batch, const u64* twist, hipStr
     hipLaunchKernelGGL((probe_kernel<V, false, 1>), dim3(batch), dim3(64), 0, s, data, batch, twist);
 }
 
-// the library's launch form (forward: one wave per workgroup, inverse: four) of body V with a first-generation stagger
-template <int V, int STAG>
-static void launch_lib(bool fwd, u64* data, uint32_t batch, const u64* twist, hipStream_t s) {
-  if (fwd)
-    hipLaunchKernelGGL((probe_kernel<V, true, 1, STAG>), dim3(batch), dim3(64), 0, s, data, batch, twist);
-  else
-    hipLaunchKernelGGL((probe_kernel<V, false, 4, STAG>), dim3((batch + 3) / 4), dim3(256), 0, s, data, batch, twist);
-}
-
-// variants past the generated ones: body 1 (the library's) in the library's launch form, plain (control) and with a
-// first-generation stagger of 25 / 50 / 100 / 200 x 64 cycles per slot (r6)
+// variants past the generated ones: body 0 in the library's launch form (forward: one wave per workgroup, inverse: four)
 static void launch_v(int v, bool fwd, u64* data, uint32_t batch, const u64* twist, hipStream_t s) {
-  switch (v) {
-    case MI_N_VARIANTS + 0: launch_lib<1, 0>(fwd, data, batch, twist, s); return;
-    case MI_N_VARIANTS + 1: launch_lib<1, 25>(fwd, data, batch, twist, s); return;
-    case MI_N_VARIANTS + 2: launch_lib<1, 50>(fwd, data, batch, twist, s); return;
-    case MI_N_VARIANTS + 3: launch_lib<1, 100>(fwd, data, batch, twist, s); return;
-    case MI_N_VARIANTS + 4: launch_lib<1, 200>(fwd, data, batch, twist, s); return;
-    default: break;
+  if (v == MI_N_VARIANTS) {
+    if (fwd)
+      hipLaunchKernelGGL((probe_kernel<0, true, 1>), dim3(batch), dim3(64), 0, s, data, batch, twist);
+    else
+      hipLaunchKernelGGL((probe_kernel<0, false, 4>), dim3((batch + 3) / 4), dim3(256), 0, s, data, batch, twist);
+    return;
   }
-  switch (v) {
-    case 0: launch<0>(fwd, data, batch, twist, s); break;
-    case 1: launch<1>(fwd, data, batch, twist, s); break;
-    case 2: launch<2>(fwd, data, batch, twist, s); break;
-    default: launch<3>(fwd, data, batch, twist, s); break;
-  }
+#define MI_LAUNCH(n) \
+  if (v == n) launch<n>(fwd, data, batch, twist, s);
+  MI_FOR_EACH_VARIANT(MI_LAUNCH)
 }
 
 int main(int argc, char** argv) {
   const uint32_t batch = argc > 1 ? (uint32_t)atoi(argv[1]) : 8192;
-  const int nv = MI_N_VARIANTS + 5;
+  const int nv = MI_N_VARIANTS + 1;
   const size_t n = (size_t)batch * 2048;
   u64 *data, *twist, *ref;
   CK(hipMalloc(&data, n * 8));
@@ -157,18 +126,14 @@ int main(int argc, char** argv) {
   hipLaunchKernelGGL(fill, dim3(32), dim3(256), 0, s, twist, (size_t)8192, 11ull);
   // bit-identity vs variant 0 (fwd then inv)
   std::vector<u64> h0(n), h1(n);
+  std::vector<int> same(nv, 1);
   for (int v = 0; v < nv; ++v) {
     hipLaunchKernelGGL(fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, data, n, 7ull);
     launch_v(v, true, data, batch, twist, s);
     launch_v(v, false, data, batch, twist, s);
     CK(hipStreamSynchronize(s));
     CK(hipMemcpy(v == 0 ? h0.data() : h1.data(), data, n * 8, hipMemcpyDeviceToHost));
-    static const int same[] = MI_SAME_MATH;
-    const bool cmp = v < MI_N_VARIANTS ? same[v] : same[1];  // extras: body 1
-    if (v && cmp && memcmp(h0.data(), h1.data(), n * 8) != 0) {
-      fprintf(stderr, "variant %d differs from variant 0\n", v);
-      return 2;
-    }
+    if (v) same[v] = memcmp(h0.data(), h1.data(), n * 8) == 0;
   }
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -176,7 +141,8 @@ int main(int argc, char** argv) {
   for (int it = 0; it < 20000; ++it) launch_v(0, it & 1 ? false : true, data, batch, twist, s);  // clock settles
   // rounds visit the variants in a rotated order, so no variant always follows the same one (the power-capped
   // clock carries heat from one timed block into the next)
-  const int K = 300, R = 2 * nv + 1;
+  // (at least 19 rounds, whatever the number of variants: the median of a variant is over its R timed blocks)
+  const int K = 300, R = std::max(2 * nv + 1, 19);
   std::vector<std::vector<double>> fw(nv), iv(nv);
   for (int r = 0; r < R; ++r)
     for (int vi = 0; vi < nv; ++vi)
@@ -194,8 +160,8 @@ int main(int argc, char** argv) {
     std::sort(fw[v].begin(), fw[v].end());
     std::sort(iv[v].begin(), iv[v].end());
     printf("{\"variant\": %d, \"batch\": %u, \"fwd_us_median\": %.2f, \"inv_us_median\": %.2f, \"fwd_us_min\": %.2f, "
-           "\"inv_us_min\": %.2f}\n",
-           v, batch, fw[v][R / 2], iv[v][R / 2], fw[v][0], iv[v][0]);
+           "\"inv_us_min\": %.2f, \"same_bits_as_v0\": %s}\n",
+           v, batch, fw[v][R / 2], iv[v][R / 2], fw[v][0], iv[v][0], same[v] ? "true" : "false");
   }
   return 0;
 }

@@ -858,6 +858,108 @@ int mi_glwe_compress128_batch(uint64_t *packed, const uint64_t *glwe, size_t pol
 int mi_glwe_extract128_batch(uint64_t *glwe, const uint64_t *packed, size_t polynomial_size, int glwe_dim,
                              size_t bodies_count, int log_modulus, size_t batch, int device, void *stream);
 
+/* ---- WoP-PBS: the bootstrap without padding bit on the f64-FFT path -------------------------------------------
+ * The device counterpart of fft_impl/fft64/crypto/wop_pbs/mod.rs (public face: algorithms/lwe_wopbs.rs), what
+ * shortint::wopbs and integer::wopbs are built on: bit extraction, circuit bootstrap, CMUX tree, rotation and vertical
+ * packing, each batched over independent evaluations.  Native 2^64 modulus only, as the reference asserts.  Device
+ * pointers, async on `stream`; stream-ordered scratch from the pool, returned before each call returns; batch = 0 is
+ * MI_OK; a NULL argument, or a shape the reference would assert on, is MI_ERR_INVALID_ARG.  Every composite is the
+ * sequence of the public stages named with it and equals that sequence bit for bit.
+ * Not provided: key generation on the device, non-native moduli, the NTT-path twins, the C++ mirror.
+ *
+ * The private functional packing keyswitch (private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext,
+ * algorithms/lwe_private_functional_packing_keyswitch.rs:20-88) against a key list:
+ *   out = - sum_{i <= in_dim} sum_l digit_l(closest_representable(lwe[i])) * key[i][l]
+ * The body word lwe[in_dim] is decomposed like the mask (a key has in_dim + 1 blocks) and nothing is added to the
+ * output.  mi_lwe_pfpksk_list_create takes the reference's LwePrivateFunctionalPackingKeyswitchKeyList layout as a
+ * device pointer: n_keys keys back to back, each in_dim + 1 blocks of `level` GLWEs of (glwe_dim + 1) *
+ * polynomial_size u64, levels stored as generate_lwe_private_functional_packing_keyswitch_key writes them
+ * (lwe_private_functional_packing_keyswitch_key_generation.rs:98-130), and prepares a private device copy (the
+ * caller's buffer may be freed afterwards; the preparation runs on `stream` and synchronises it).  The argument rules
+ * of mi_lwe_pksk_create, and: n_keys * (glwe_dim + 1) * polynomial_size in [1, 2^24); MI_ERR_UNSUPPORTED when
+ * (in_dim + 1) * level * ceil((base_log + 1) / 8) >= 2^17 (the GEMM-depth bound of mi_lwe_ksk_create with the body
+ * block counted). */
+typedef struct mi_lwe_pfpksk_list mi_lwe_pfpksk_list;
+int mi_lwe_pfpksk_list_create(const uint64_t *pfpksk_list, size_t n_keys, size_t in_dim, int glwe_dim,
+                              size_t polynomial_size, int base_log, int level, int device, void *stream,
+                              mi_lwe_pfpksk_list **out_key);
+int mi_lwe_pfpksk_list_destroy(mi_lwe_pfpksk_list *key);
+int mi_lwe_pfpksk_list_info(const mi_lwe_pfpksk_list *key, size_t *n_keys, size_t *in_dim, int *glwe_dim,
+                            size_t *polynomial_size, int *base_log, int *level);
+/* Every key of the list applied to every input: glwe_out[b * n_keys + j] ((glwe_dim + 1) * polynomial_size u64) is
+ * key j applied to lwe_in[b] (in_dim + 1 u64), one GEMM on the int8 matrix cores whose digit operand all keys share.
+ * With n_keys = glwe_dim + 1 the n_keys GLWEs of an input are one GGSW level matrix.  Bit-exact. */
+int mi_lwe_pfpks_batch(const mi_lwe_pfpksk_list *key, uint64_t *glwe_out, const uint64_t *lwe_in, size_t n_lwe,
+                       void *stream);
+
+/* mi_fft64_ext_product_batch / mi_fft64_cmux_batch with one Fourier GGSW per item, the semantics of
+ * mi_ext_product_ntt64_batch_indexed / mi_cmux_ntt64_batch_indexed: item b uses GGSW ggsw_index[b] (device u32 array of
+ * `batch` entries) of the n_ggsw GGSWs stored back to back in ggsw_fourier_list; an item whose index is >= n_ggsw is
+ * left untouched (both its GLWEs).  Both engines; per item the arithmetic of the shared-GGSW call, bit for bit. */
+int mi_fft64_ext_product_batch_indexed(const mi_fft64_plan *plan, uint64_t *out_glwe, const uint64_t *in_glwe,
+                                       const double *ggsw_fourier_list, const uint32_t *ggsw_index, size_t n_ggsw,
+                                       int k, int base_log, int level, size_t batch, void *stream);
+int mi_fft64_cmux_batch_indexed(const mi_fft64_plan *plan, uint64_t *ct0, uint64_t *ct1,
+                                const double *ggsw_fourier_list, const uint32_t *ggsw_index, size_t n_ggsw, int k,
+                                int base_log, int level, size_t batch, void *stream);
+
+/* extract_bits (wop_pbs/mod.rs:61-220) over a batch: lwe_in[b] (k N + 1 u64 of the bootstrap key's output) gives
+ * lwe_list_out[b * n_bits + j] (ksk output size, n + 1 u64), j = 0 the most significant of the n_bits bits from bit
+ * delta_log up, each encoded in the top bit.  Per bit from the least significant: left shift by
+ * 64 - delta_log - bit - 1, mi_lwe_keyswitch_batch, store, + 2^62 on the body, mi_fft64_pbs_batch (standard modulus
+ * switch) with the trivial accumulator of body -2^(delta_log - 1 + bit), + 2^(delta_log + bit - 1) on the output body,
+ * subtract from the running input; the last bit stops after the keyswitch.  All items advance one bit per step.
+ * ksk: k N -> n of bsk; delta_log + n_bits <= 64, delta_log >= 1 when n_bits > 1. */
+int mi_fft64_extract_bits_batch(const mi_fft64_pbs_key *bsk, const mi_lwe_ksk *ksk, uint64_t *lwe_list_out,
+                                const uint64_t *lwe_in, int delta_log, size_t n_bits, size_t batch, void *stream);
+/* circuit_bootstrap_boolean + homomorphic_shift_boolean (:238-435) over a batch of boolean LWEs (n + 1 u64, the bit at
+ * delta_log).  ggsw_std_out[b]: level_cbs x n_keys GLWEs of the pfpksk's output size, output index 0 = decomposition
+ * level level_cbs (the layout the f64 external product reads); ggsw_fourier_out[b]: the same through forward_as_torus
+ * in out_plan's order (fill_with_forward_fourier), level_cbs * n_keys^2 * N / 2 complex.  Either may be NULL, not
+ * both.  The sequence: one mi_fft64_pbs_batch_lut_indexed over batch * level_cbs items, item b * level_cbs + i =
+ * lwe_in[b] * 2^(63 - delta_log) with 2^62 added to the body, accumulator body -2^(63 - base_log_cbs * (level_cbs -
+ * i)), the same constant added to the output body; one mi_lwe_pfpks_batch over those LWEs; mi_bsk_to_fourier64.
+ * pfpksk: in_dim = k N of bsk, n_keys = glwe_dim + 1; out_plan: the pfpksk's polynomial size. */
+int mi_fft64_circuit_bootstrap_boolean_batch(const mi_fft64_pbs_key *bsk, const mi_lwe_pfpksk_list *pfpksk,
+                                             const mi_fft64_plan *out_plan, uint64_t *ggsw_std_out,
+                                             double *ggsw_fourier_out, const uint64_t *lwe_in, size_t batch,
+                                             int delta_log, int base_log_cbs, int level_cbs, void *stream);
+/* The GGSW lists of the three calls below: batch x ggsw_stride Fourier GGSWs, item b's at b * ggsw_stride; a call
+ * reads GGSWs [ggsw_first, ggsw_first + count) of each item (batch * ggsw_stride < 2^32).  Every item evaluates
+ * n_outputs functions with the same GGSWs.
+ *
+ * cmux_tree_memory_optimized (:459-583): lut_polys holds n_outputs x n_polys polynomials (N u64, shared by the batch),
+ * n_polys = 2^r (else MI_ERR_INVALID_ARG); glwe_out[b * n_outputs + o] = the tree over output o's polynomials as trivial
+ * GLWEs, layer j doing 2^(r-1-j) CMUXes t0 + G (.) (t1 - t0) with GGSW ggsw_first + r - 1 - j of the item; r = 0 writes
+ * the trivial GLWE.  Breadth-first: a layer of all trees in the chunk is one mi_fft64_cmux_batch_indexed call, in
+ * place; the chunk is the whole trees (2^r GLWEs each) that fit 256 MiB of scratch, at least one tree. */
+int mi_fft64_cmux_tree_batch(const mi_fft64_plan *plan, uint64_t *glwe_out, const uint64_t *lut_polys, size_t n_polys,
+                             size_t n_outputs, const double *ggsw_fourier_list, size_t ggsw_stride, size_t ggsw_first,
+                             size_t r, int k, int base_log, int level, size_t batch, void *stream);
+/* blind_rotate_assign (:838-863), in place on glwe[b * n_outputs + o]: from GGSW ggsw_first + n_rot - 1 down to
+ * ggsw_first, ct1 = ct0 / X^d (polynomial_wrapping_monic_monomial_div_assign: d acts mod 2N), d <- 2 d from d = 1, then
+ * mi_fft64_cmux_batch_indexed(ct0, ct1). */
+int mi_fft64_wop_blind_rotate_batch(const mi_fft64_plan *plan, uint64_t *glwe, size_t n_outputs,
+                                    const double *ggsw_fourier_list, size_t ggsw_stride, size_t ggsw_first,
+                                    size_t n_rot, int k, int base_log, int level, size_t batch, void *stream);
+/* vertical_packing (:771-825): mi_fft64_cmux_tree_batch over the first floor(log2(n_polys)) GGSWs of each item (none
+ * when the item has fewer), mi_fft64_wop_blind_rotate_batch over the rest, mi_sample_extract_batch at degree 0;
+ * lwe_out is batch x n_outputs x (k N + 1).  Where the reference would panic (n_polys not a power of two; no tree but
+ * more than one polynomial) MI_ERR_INVALID_ARG. */
+int mi_fft64_vertical_packing_batch(const mi_fft64_plan *plan, uint64_t *lwe_out, const uint64_t *lut_polys,
+                                    size_t n_polys, size_t n_outputs, const double *ggsw_fourier_list, size_t n_ggsw,
+                                    int k, int base_log, int level, size_t batch, void *stream);
+/* circuit_bootstrap_boolean_vertical_packing (:638-732; circuit_bootstrap_boolean_vertical_packing_lwe_ciphertext_
+ * list_mem_optimized, algorithms/lwe_wopbs.rs:644-698): mi_fft64_circuit_bootstrap_boolean_batch of each item's n_bits
+ * input LWEs (lwe_list_in: batch x n_bits x (n + 1), most significant first, as extract_bits writes them) at
+ * delta_log = 63 into a Fourier GGSW list in scratch, then mi_fft64_vertical_packing_batch of the n_outputs chunks of
+ * n_polys polynomials of big_lut (shared by the batch) in out_plan; lwe_out: batch x n_outputs x (k' N' + 1) of the
+ * pfpksk's GLWE shape. */
+int mi_fft64_circuit_bootstrap_boolean_vertical_packing_batch(
+    const mi_fft64_pbs_key *bsk, const mi_lwe_pfpksk_list *pfpksk, const mi_fft64_plan *out_plan, uint64_t *lwe_out,
+    const uint64_t *lwe_list_in, size_t n_bits, const uint64_t *big_lut, size_t n_polys, size_t n_outputs,
+    int base_log_cbs, int level_cbs, size_t batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,6 +281,38 @@ int mi_fft64_cmux_batch(const mi_fft64_plan* plan, uint64_t* ct0, uint64_t* ct1,
   return e == hipSuccess ? MI_OK : hip_fail(e, "fft64 cmux launch");
 }
 
+// one GGSW per item (the NTT path's mi_ext_product_ntt64_batch_indexed / mi_cmux_ntt64_batch_indexed on the f64 path)
+static int ext_indexed(bool cmux, const mi_fft64_plan* plan, uint64_t* out, uint64_t* in, const double* ggsw_list,
+                       const uint32_t* ggsw_index, size_t n_ggsw, int k, int base_log, int level, size_t batch,
+                       void* stream) {
+  int st = check_shape(plan, k, base_log, level);
+  if (st != MI_OK) return st;
+  if (batch == 0) return MI_OK;
+  if (!out || !in || !ggsw_list || !ggsw_index) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
+  if (batch > 0x7FFFFFFFull) return fail(MI_ERR_INVALID_ARG, "batch too large");
+  if (n_ggsw == 0 || n_ggsw > 0xFFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "n_ggsw out of range");
+  DeviceGuard g(plan->device);
+  const hipError_t e =
+      plan->generic ? mi::launch_fftg_ext_product_indexed(k, cmux, out, in, ggsw_list, ggsw_index, n_ggsw, batch,
+                                                          base_log, level, plan->gtables, (hipStream_t)stream)
+                    : mi::launch_fft64_ext_product_indexed(k, cmux, out, in, ggsw_list, ggsw_index, n_ggsw, batch,
+                                                           base_log, level, plan->tables, (hipStream_t)stream);
+  return e == hipSuccess ? MI_OK : hip_fail(e, cmux ? "fft64 cmux launch" : "fft64 external product launch");
+}
+
+int mi_fft64_ext_product_batch_indexed(const mi_fft64_plan* plan, uint64_t* out_glwe, const uint64_t* in_glwe,
+                                       const double* ggsw_fourier_list, const uint32_t* ggsw_index, size_t n_ggsw,
+                                       int k, int base_log, int level, size_t batch, void* stream) {
+  return ext_indexed(false, plan, out_glwe, const_cast<uint64_t*>(in_glwe), ggsw_fourier_list, ggsw_index, n_ggsw, k,
+                     base_log, level, batch, stream);
+}
+
+int mi_fft64_cmux_batch_indexed(const mi_fft64_plan* plan, uint64_t* ct0, uint64_t* ct1,
+                                const double* ggsw_fourier_list, const uint32_t* ggsw_index, size_t n_ggsw, int k,
+                                int base_log, int level, size_t batch, void* stream) {
+  return ext_indexed(true, plan, ct0, ct1, ggsw_fourier_list, ggsw_index, n_ggsw, k, base_log, level, batch, stream);
+}
+
 int mi_fft64_pbs_key_create(const mi_fft64_plan* plan, const double* fbsk, size_t n_lwe, int k, int base_log,
                             int level, mi_fft64_pbs_key** out_key) {
   if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");

@@ -1,5 +1,5 @@
-// c_api_keyswitch.cpp — the keyswitch family of the C ABI: the three prepared keys (mi_lwe_ksk, mi_lwe_ksk32,
-// mi_lwe_pksk) over one shared core, the two LWE modulus switches, the packing keyswitch and the GLWE compression
+// c_api_keyswitch.cpp — the keyswitch family of the C ABI: the four prepared keys (mi_lwe_ksk, mi_lwe_ksk32,
+// mi_lwe_pksk, mi_lwe_pfpksk_list) over one shared core, the two LWE modulus switches, the packing keyswitch and the GLWE compression
 // (kernels: keyswitch.hip, packing_keyswitch.hip), and their u128 twins of the noise-squashing compression
 // (mi_lwe_pksk128, packing_keyswitch128.hip).
 #include <new>
@@ -38,6 +38,12 @@ struct mi_lwe_pksk {
   size_t polynomial_size = 0;
 };
 
+struct mi_lwe_pfpksk_list {
+  KsKey core;  // KsMode::Pfpks: n_keys (k + 1) N key columns over in_dim + 1 blocks, no body column
+  int glwe_dim = 0;
+  size_t polynomial_size = 0;
+};
+
 struct mi_lwe_pksk128 {
   int device = 0;
   mi::Pks128Geometry geo;
@@ -51,7 +57,9 @@ namespace {
 // The range rules of the three creates, in their common order.  `own` is the message of the caller's own failed rule
 // (the output dimension, the KS32 output modulus, the GLWE shape) or nullptr: those rules sit between the input
 // dimension and the decomposition.  `top`: the largest base_log * level of the key kind.
-int check_ks_range(size_t in_dim, const char* own, int base_log, int level, int top) {
+// `blocks`: the key's blocks of `level` rows, the GEMM's depth in digits: in_dim, or in_dim + 1 where the body word is
+// decomposed too (0: in_dim).
+int check_ks_range(size_t in_dim, const char* own, int base_log, int level, int top, size_t blocks = 0) {
   if (in_dim == 0 || in_dim > 0xFFFFFFull) return fail(MI_ERR_INVALID_ARG, "lwe dimension out of range");
   if (own) return fail(MI_ERR_INVALID_ARG, own);
   // SignedDecomposer::new (decomposer.rs): base_log * level < Scalar::BITS, both >= 1; KS32 (lwe_keyswitch.rs:
@@ -61,8 +69,9 @@ int check_ks_range(size_t in_dim, const char* own, int base_log, int level, int 
   // u128 keys only (top = 127): a digit is held in an int64 and split into at most 8 signed bytes
   if (base_log > 63) return fail(MI_ERR_UNSUPPORTED, "base_log above 63 is not supported (a digit must fit 64 bits)");
   // exact int32 accumulation on the int8 matrix cores: GEMM depth in_dim * level * bytes-per-digit < 2^17
-  if ((double)in_dim * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
-    return fail(MI_ERR_UNSUPPORTED, "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
+  if ((double)(blocks ? blocks : in_dim) * level * mi::ks_digit_bytes_per_term(base_log) >= 131072.0)
+    return fail(MI_ERR_UNSUPPORTED, blocks ? "(in_dim + 1) * level * ceil((base_log + 1) / 8) must stay below 2^17"
+                                           : "in_dim * level * ceil((base_log + 1) / 8) must stay below 2^17");
   return MI_OK;
 }
 
@@ -313,6 +322,56 @@ int mi_lwe_packing_keyswitch_batch(const mi_lwe_pksk* key, uint64_t* glwe_out, c
   const hipError_t e = mi::launch_packing_keyswitch(glwe_out, lwe_in, k.frag, t.ptr(), digits.ptr(), partials.ptr(),
                                                     n_lwe, lwe_per_glwe, key->polynomial_size, k.geo, plan, s);
   return e == hipSuccess ? MI_OK : hip_fail(e, "packing keyswitch launch");
+}
+
+// ---- LWE private functional packing keyswitch against a key list (tfhe/src/core_crypto/algorithms/
+// lwe_private_functional_packing_keyswitch.rs:20-88; the list: entities/lwe_private_functional_packing_keyswitch_key_
+// list.rs; the circuit bootstrap's use of it: fft_impl/fft64/crypto/wop_pbs/mod.rs:390-435) ------------------------
+
+int mi_lwe_pfpksk_list_create(const uint64_t* pfpksk_list, size_t n_keys, size_t in_dim, int glwe_dim,
+                              size_t polynomial_size, int base_log, int level, int device, void* stream,
+                              mi_lwe_pfpksk_list** out_key) {
+  if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
+  *out_key = nullptr;
+  if (!pfpksk_list) return fail(MI_ERR_INVALID_ARG, "pfpksk_list is NULL");
+  const size_t n = polynomial_size;
+  const char* own = nullptr;
+  if (n == 0 || (n & (n - 1)) != 0)
+    own = "polynomial size must be a power of two";
+  else if (glwe_dim < 1 || n > 0xFFFFFFull || ((size_t)glwe_dim + 1) * n > 0xFFFFFFull)
+    own = "glwe size out of range";
+  else if (n_keys == 0 || n_keys > 0xFFFFFFull || n_keys * ((size_t)glwe_dim + 1) * n > 0xFFFFFFull)
+    own = "n_keys * (glwe_dim + 1) * polynomial_size must be in [1, 2^24)";
+  int st = check_ks_range(in_dim, own, base_log, level, 63, in_dim + 1);
+  if (st != MI_OK) return st;
+  mi::KsGeometry geo{mi::KsMode::Pfpks, in_dim, n_keys * ((size_t)glwe_dim + 1) * n, base_log, level, 64, 0, n_keys};
+  st = ks_create(out_key, pfpksk_list, geo, device, stream, "private functional packing keyswitch key list");
+  if (st != MI_OK) return st;
+  (*out_key)->glwe_dim = glwe_dim;
+  (*out_key)->polynomial_size = n;
+  return MI_OK;
+}
+
+int mi_lwe_pfpksk_list_destroy(mi_lwe_pfpksk_list* key) { return ks_destroy(key); }
+
+int mi_lwe_pfpksk_list_info(const mi_lwe_pfpksk_list* key, size_t* n_keys, size_t* in_dim, int* glwe_dim,
+                            size_t* polynomial_size, int* base_log, int* level) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  if (n_keys) *n_keys = key->core.geo.n_keys;
+  if (in_dim) *in_dim = key->core.geo.in_dim;
+  if (glwe_dim) *glwe_dim = key->glwe_dim;
+  if (polynomial_size) *polynomial_size = key->polynomial_size;
+  if (base_log) *base_log = key->core.geo.base_log;
+  if (level) *level = key->core.geo.level;
+  return MI_OK;
+}
+
+// One GEMM: the rows are the input LWEs, the columns the n_keys GLWEs of every row back to back, which is the output's
+// own layout (glwe_out[b * n_keys + j]).
+int mi_lwe_pfpks_batch(const mi_lwe_pfpksk_list* key, uint64_t* glwe_out, const uint64_t* lwe_in, size_t n_lwe,
+                       void* stream) {
+  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
+  return run_keyswitch(key->core, glwe_out, lwe_in, n_lwe, stream);
 }
 
 // ---- CompressedModulusSwitchedGlweCiphertext (entities/compressed_modulus_switched_glwe_ciphertext.rs:169-256) ---

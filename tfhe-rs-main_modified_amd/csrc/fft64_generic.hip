@@ -202,6 +202,22 @@ struct MacSrc {
   }
 };
 
+// MacSrc with one GGSW per item: item b multiplies by GGSW idx[b] of the list (the same load on another key address);
+// an item whose index is >= n_ggsw contributes zeros, and AccSinkIdx drops them
+struct MacSrcIdx {
+  MacSrc m;  // m.g = the list
+  const uint32_t* idx;
+  uint32_t n_ggsw;
+  uint64_t ggsw_len;  // complex per GGSW
+  __device__ __forceinline__ cplx load(uint64_t row, uint32_t x) const {
+    const uint32_t gi = idx[(row >> m.logr) / m.kp1];
+    if (gi >= n_ggsw) return cplx{0.0, 0.0};
+    MacSrc one = m;
+    one.g = m.g + gi * ggsw_len;
+    return one.load(row, x);
+  }
+};
+
 // backward_as_torus (convert_[add_]backward_torus, fft/mod.rs:545-565): untwist (x 1/M folded into untw), exact
 // from_torus of both halves, stored or added
 struct TorusSink {
@@ -230,6 +246,16 @@ struct AccSink {
     const uint32_t m = 1u << (logn - 1);
     add_torus(x[n], y.re);
     add_torus(x[n + m], y.im);
+  }
+};
+
+// AccSink that leaves the items with an out-of-range GGSW index untouched
+struct AccSinkIdx {
+  AccSink a;
+  const uint32_t* idx;
+  uint32_t n_ggsw, kp1;
+  __device__ __forceinline__ void store(uint64_t p, uint32_t n, cplx v) const {
+    if (idx[p / kp1] < n_ggsw) a.store(p, n, v);
   }
 };
 
@@ -482,6 +508,14 @@ __global__ __launch_bounds__(256) void sub_assign_kernel(u64* __restrict__ a, co
   for (uint64_t i = grid_stride_start(); i < count; i += grid_stride()) a[i] -= b[i];
 }
 
+// the same for the items whose GGSW index is in range (`per` words per item)
+__global__ __launch_bounds__(256) void sub_assign_idx_kernel(u64* __restrict__ a, const u64* __restrict__ b,
+                                                             uint64_t count, uint64_t per,
+                                                             const uint32_t* __restrict__ idx, uint32_t n_ggsw) {
+  for (uint64_t i = grid_stride_start(); i < count; i += grid_stride())
+    if (idx[i / per] < n_ggsw) a[i] -= b[i];
+}
+
 // ---- launch helpers ---------------------------------------------------------------------------------------
 template <int LOGC, bool INV, class Src, class Dst>
 hipError_t rows_at(Src src, Dst dst, uint64_t rows, const cplx* wm, uint32_t logm, hipStream_t s) {
@@ -646,8 +680,10 @@ hipError_t launch_fftg_reorder(double* out, const double* in, size_t polys, bool
   return e;
 }
 
-hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, size_t batch,
-                                   int base_log, int level, const FftGenTables& t, hipStream_t s) {
+// idx == nullptr: one shared GGSW; else item b uses GGSW idx[b] of the n_ggsw in `ggsw` (out of range: untouched)
+static hipError_t fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw,
+                                   const uint32_t* idx, size_t n_ggsw, size_t batch, int base_log, int level,
+                                   const FftGenTables& t, hipStream_t s) {
   using namespace fft::gen;
   if (batch == 0) return hipSuccess;
   const Geo g = geo(t);
@@ -665,17 +701,39 @@ hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* gl
     const uint64_t nb = std::min(chunk, batch - b0);
     uint64_t* o = out + b0 * per;
     uint64_t* in = glwe + b0 * per;
+    const uint32_t* ix = idx ? idx + b0 : nullptr;
     if (cmux) {
-      hipLaunchKernelGGL(sub_assign_kernel, dim3(blocks_for(nb * per)), dim3(256), 0, s, in, (const uint64_t*)o,
-                         (uint64_t)(nb * per));
+      if (ix)
+        hipLaunchKernelGGL(sub_assign_idx_kernel, dim3(blocks_for(nb * per)), dim3(256), 0, s, in, (const uint64_t*)o,
+                           (uint64_t)(nb * per), (uint64_t)per, ix, (uint32_t)n_ggsw);
+      else
+        hipLaunchKernelGGL(sub_assign_kernel, dim3(blocks_for(nb * per)), dim3(256), 0, s, in, (const uint64_t*)o,
+                           (uint64_t)(nb * per));
       if ((e = hipGetLastError()) != hipSuccess) break;
     }
     e = forward(g, GlweDigitSrc{in, g.tw, g.logn, kp1, lv, base_log}, d, nb * lv * kp1, s);
     if (e != hipSuccess) break;
-    e = inverse(g, MacSrc{d, gg, g.logm, g.logc, g.logr, kp1, lv}, AccSink{o, g.untw, g.logn}, y, nb * kp1, s);
+    const MacSrc mac{d, gg, g.logm, g.logc, g.logr, kp1, lv};
+    const AccSink sink{o, g.untw, g.logn};
+    if (ix)
+      e = inverse(g, MacSrcIdx{mac, ix, (uint32_t)n_ggsw, ((uint64_t)lv * kp1 * kp1) << g.logm},
+                  AccSinkIdx{sink, ix, (uint32_t)n_ggsw, kp1}, y, nb * kp1, s);
+    else
+      e = inverse(g, mac, sink, y, nb * kp1, s);
   }
   const hipError_t ef = mi::scratch_free(scratch, s);
   return e != hipSuccess ? e : ef;
+}
+
+hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, size_t batch,
+                                   int base_log, int level, const FftGenTables& t, hipStream_t s) {
+  return fftg_ext_product(k, cmux, out, glwe, ggsw, nullptr, 0, batch, base_log, level, t, s);
+}
+
+hipError_t launch_fftg_ext_product_indexed(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw_list,
+                                           const uint32_t* idx, size_t n_ggsw, size_t batch, int base_log, int level,
+                                           const FftGenTables& t, hipStream_t s) {
+  return fftg_ext_product(k, cmux, out, glwe, ggsw_list, idx, n_ggsw, batch, base_log, level, t, s);
 }
 
 // The chunk loop and the lanes are run_blind_rotation's (pbs_passes.hpp), as launch_pbs_large's: one lane's

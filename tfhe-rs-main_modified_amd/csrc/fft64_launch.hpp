@@ -29,6 +29,10 @@ hipError_t launch_fft64_bwd_torus(uint64_t* std_, const double* fourier, size_t 
                                   hipStream_t s);
 hipError_t launch_fft64_ext_product(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, size_t batch,
                                     int base_log, int level, const FftTables& t, hipStream_t s);
+// one GGSW per item: item b uses GGSW idx[b] (device u32) of the n_ggsw in ggsw_list; idx[b] >= n_ggsw: untouched
+hipError_t launch_fft64_ext_product_indexed(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw_list,
+                                            const uint32_t* idx, size_t n_ggsw, size_t batch, int base_log, int level,
+                                            const FftTables& t, hipStream_t s);
 hipError_t launch_fft64_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const PbsIo& io, const double* fbsk,
                             size_t n_lwe, size_t batch, int base_log, int level, int ms_mode, const FftTables& t,
                             hipStream_t s);
@@ -60,6 +64,9 @@ hipError_t launch_fftg_reorder(double* out, const double* in, size_t polys, bool
                                hipStream_t s);
 hipError_t launch_fftg_ext_product(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, size_t batch,
                                    int base_log, int level, const FftGenTables& t, hipStream_t s);
+hipError_t launch_fftg_ext_product_indexed(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw_list,
+                                           const uint32_t* idx, size_t n_ggsw, size_t batch, int base_log, int level,
+                                           const FftGenTables& t, hipStream_t s);
 hipError_t launch_fftg_pbs(int k, uint64_t* out, const uint64_t* lwe_in, const PbsIo& io, const double* fbsk,
                            size_t n_lwe, size_t batch, int base_log, int level, int ms_mode, const FftGenTables& t,
                            hipStream_t s);

@@ -255,6 +255,21 @@ __global__ __launch_bounds__(64 * (K + 1)) void ext_product_kernel(u64* __restri
   __shared__ Wg<K, 1> wg;
   ext_product_body<K, CMUX, L1, 1>(out, glwe, ggsw, batch, base_log, level, tb, wg);
 }
+// One GGSW per item: workgroup b (one item) runs the same body with GGSW idx[b] of the
+// list; an index >= n_ggsw ends the whole workgroup before it touches anything (uniform: before any barrier).
+template <int K, bool CMUX, bool L1>
+__global__ __launch_bounds__(64 * (K + 1)) void ext_product_indexed_kernel(u64* __restrict__ out,
+                                                                           u64* __restrict__ glwe,
+                                                                           const cplx* __restrict__ ggsw_list,
+                                                                           const uint32_t* __restrict__ idx,
+                                                                           uint32_t n_ggsw, int base_log, int level,
+                                                                           Tables tb) {
+  __shared__ Wg<K, 1> wg;
+  const uint32_t g = idx[blockIdx.x];
+  if (g >= n_ggsw) return;
+  const size_t ggsw_len = (size_t)level * (K + 1) * (K + 1) * M;
+  ext_product_body<K, CMUX, L1, 1>(out, glwe, ggsw_list + (size_t)g * ggsw_len, gridDim.x, base_log, level, tb, wg);
+}
 // ---- programmable bootstrap (bootstrap.rs:481-521 + blind_rotate_assign :294-381) -------------------
 // lwe_in: batch x (n + 1); lut: (K+1) x N shared; fbsk: n x level x (K+1) x (K+1) x M complex;
 // lwe_out: batch x (K N + 1).  ms_mode: 0 standard, 1 centered, 2 pre-switched (values in [0, 2N)).
@@ -424,6 +439,27 @@ static hipError_t ext_one(uint64_t* out, uint64_t* glwe, const fft::cplx* g, siz
   return hipGetLastError();
 }
 
+template <int K, bool CMUX, bool L1>
+static hipError_t ext_one_indexed(uint64_t* out, uint64_t* glwe, const fft::cplx* g, const uint32_t* idx,
+                                  size_t n_ggsw, size_t batch, int base_log, int level, const FftTables& t,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL((fft::ext_product_indexed_kernel<K, CMUX, L1>), dim3((unsigned)batch), dim3(64 * (K + 1)), 0, s,
+                     out, glwe, g, idx, (uint32_t)n_ggsw, base_log, level, tables(t));
+  return hipGetLastError();
+}
+
+template <int K>
+static hipError_t ext_k_indexed(bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, const uint32_t* idx,
+                                size_t n_ggsw, size_t batch, int base_log, int level, const FftTables& t,
+                                hipStream_t s) {
+  const auto* g = reinterpret_cast<const fft::cplx*>(ggsw);
+  if (level == 1)
+    return cmux ? ext_one_indexed<K, true, true>(out, glwe, g, idx, n_ggsw, batch, base_log, level, t, s)
+                : ext_one_indexed<K, false, true>(out, glwe, g, idx, n_ggsw, batch, base_log, level, t, s);
+  return cmux ? ext_one_indexed<K, true, false>(out, glwe, g, idx, n_ggsw, batch, base_log, level, t, s)
+              : ext_one_indexed<K, false, false>(out, glwe, g, idx, n_ggsw, batch, base_log, level, t, s);
+}
+
 template <int K>
 static hipError_t ext_k(bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw, size_t batch, int base_log,
                         int level, const FftTables& t, hipStream_t s) {
@@ -440,6 +476,15 @@ hipError_t launch_fft64_ext_product(int k, bool cmux, uint64_t* out, uint64_t* g
   if (batch == 0) return hipSuccess;
   if (k == 1) return ext_k<1>(cmux, out, glwe, ggsw, batch, base_log, level, t, s);
   if (k == 2) return ext_k<2>(cmux, out, glwe, ggsw, batch, base_log, level, t, s);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_fft64_ext_product_indexed(int k, bool cmux, uint64_t* out, uint64_t* glwe, const double* ggsw_list,
+                                            const uint32_t* idx, size_t n_ggsw, size_t batch, int base_log, int level,
+                                            const FftTables& t, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  if (k == 1) return ext_k_indexed<1>(cmux, out, glwe, ggsw_list, idx, n_ggsw, batch, base_log, level, t, s);
+  if (k == 2) return ext_k_indexed<2>(cmux, out, glwe, ggsw_list, idx, n_ggsw, batch, base_log, level, t, s);
   return hipErrorInvalidValue;
 }
 

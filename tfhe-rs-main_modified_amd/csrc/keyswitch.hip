@@ -27,6 +27,11 @@
 //     column tile x 8 planes = 32 accumulators of 16x16 i32 (128 AGPRs, two waves per SIMD).  Blocks
 //     are mapped XCD-aware: the workgroups one XCD runs together cover 8 row groups x 4 column groups,
 //     so the fragments they share are re-read from that XCD's L2.
+// The private functional packing keyswitch against a key list (KsMode::Pfpks; lwe_private_functional_packing_
+// keyswitch.rs:20-88) is the same GEMM with two differences the Shape carries: the body word is one more decomposed
+// coefficient (in_dim + 1 blocks of digit rows, no output column receives the body), and the columns are those of the
+// n_keys keys of the list side by side (ksk_prepare_kernel gathers column c of key j at GEMM column j (k+1) N + c), so
+// all keys share one digit operand and a row of the product is the n_keys output GLWEs back to back.
 // Fragment maps (gfx950): lane l holds row/column (l & 15) of the tile and the 16 consecutive k of
 // group l >> 4 — the same k map for A and B, so the k order inside a block does not matter; C/D:
 // col = l & 15, row = 4 (l >> 4) + reg (cdna_hip_programming.md §3).
@@ -54,6 +59,13 @@ struct Shape {
   uint32_t body_log;  // KS32 (keyswitch_lwe_ciphertext_with_scalar_change): the output modulus 2^body_log
   uint32_t body_col;  // the output column that receives the input body: out_size - 1 (LWE), k N (packing)
   uint32_t pre_rounded;  // packing keyswitch: digits of closest_representable(a_i) (decomp_init)
+  // private functional packing keyswitch (KsMode::Pfpks): in_dim counts the body word too (every word of the input row
+  // is decomposed, no output column receives it: body_col = ~0), and the key is a list of n_keys keys of key_cols
+  // columns each, key_stride words apart, which share the digit operand.  Every other mode: in_stride = in_dim + 1,
+  // key_cols = out_size (one key).
+  uint32_t in_stride;   // words per input row
+  uint32_t key_cols;    // columns of one key of the list
+  uint64_t key_stride;  // words from one key of the list to the next
 };
 
 __device__ __forceinline__ uint4 pack16(const int8_t (&b)[16]) {
@@ -115,7 +127,11 @@ __global__ __launch_bounds__(256) void ksk_prepare_kernel(uint4* __restrict__ fr
     for (int j = 0; j < 16; ++j) {
       const uint32_t k = kb * 64 + 16 * (lane >> 4) + j;
       const uint32_t row = k / s.nd, sh = 8 * (k % s.nd);
-      const u64 x = (k < s.K && col < s.out_size) ? (u64)ksk[(uint64_t)row * s.out_size + col] << sh : 0;
+      // column col is column col % key_cols of key col / key_cols (one key: key_cols = out_size)
+      const uint32_t kj = col / s.key_cols, kc = col - kj * s.key_cols;
+      const u64 x = (k < s.K && col < s.out_size)
+                        ? (u64)ksk[(uint64_t)kj * s.key_stride + (uint64_t)row * s.key_cols + kc] << sh
+                        : 0;
       b[j] = signed_byte(x, (int)t);
     }
     frag[idx] = pack16(b);
@@ -135,7 +151,7 @@ __global__ __launch_bounds__(256) void ks_digits_kernel(uint4* __restrict__ afra
     const uint32_t mi = piece % GM, kb = (piece / GM) % s.KB, mg = (uint32_t)(piece / GM / s.KB);
     const uint32_t row = (mg * GM + mi) * 16 + (lane & 15);
     int8_t b[16];
-    const u64* x = lwe_in + (uint64_t)row * (s.in_dim + 1);
+    const u64* x = lwe_in + (uint64_t)row * s.in_stride;
     const int bl = (int)s.base_log, lv = (int)s.level;
     const bool pre = s.pre_rounded != 0;
     // digit column k = (i * level + li) * nd + sb, walked incrementally: 3 divisions per thread, not 3 per
@@ -195,7 +211,7 @@ __global__ __launch_bounds__(256) void ks_digits_l_kernel(uint4* __restrict__ af
     const uint32_t pidx = q * 256 + t, R = pidx / CPW, cw = pidx % CPW;  // row in the group, coefficient in the span
     const uint32_t kbi = cw / CPB, c = cw % CPB;
     const uint32_t row = mg * GM * 16 + R, i = kb0 * CPB + cw;
-    const u64 x = (row < batch && i < s.in_dim) ? lwe_in[(uint64_t)row * (s.in_dim + 1) + i] : 0;
+    const u64 x = (row < batch && i < s.in_dim) ? lwe_in[(uint64_t)row * s.in_stride + i] : 0;
     u64 state = core::decomp_init<u64>(x, bl, LEVEL, s.pre_rounded != 0);  // 0 decomposes to 0 at every level (padding rows / columns)
     W w = 0;
 #pragma unroll
@@ -372,7 +388,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ks_gemm_kernel(void* __restrict__ 
         u64 v = 0;
 #pragma unroll
         for (int t = 0; t < NPL; ++t) v += (u64)(int64_t)acc[m][c][t][r] << (8 * t);
-        u64 base = is_body ? lwe_in[(uint64_t)row * (s.in_dim + 1) + s.in_dim] : 0;
+        u64 base = is_body ? lwe_in[(uint64_t)row * s.in_stride + s.in_stride - 1] : 0;
         if constexpr (OUT32) {
           if (is_body) base = closest_representable(base, s.body_log) >> 32;
           static_cast<uint32_t*>(out_v)[(uint64_t)row * s.out_size + col] = (uint32_t)(base - v);
@@ -435,17 +451,21 @@ static ks::Shape ks_shape(const KsGeometry& g) {
   const bool k32 = g.mode == KsMode::Ks32;
   const uint32_t gn = k32 ? ks::Geo<true>::GN : ks::Geo<false>::GN;
   ks::Shape s;
-  s.in_dim = (uint32_t)g.in_dim;
+  const bool pf = g.mode == KsMode::Pfpks;
+  s.in_dim = (uint32_t)(g.in_dim + (pf ? 1 : 0));  // the decomposed words of a row
+  s.in_stride = (uint32_t)g.in_dim + 1;
   s.out_size = (uint32_t)g.out_size;
   s.level = (uint32_t)g.level;
   s.base_log = (uint32_t)g.base_log;
   s.nd = (uint32_t)ks_digit_bytes_per_term(g.base_log);
-  s.K = (uint32_t)(g.in_dim * (size_t)g.level * s.nd);
+  s.K = (uint32_t)(s.in_dim * (size_t)g.level * s.nd);
   s.KB = (s.K + 63) / 64;
   s.CT = (s.out_size + 16 * gn - 1) / (16 * gn) * gn;  // whole column groups
   s.body_log = k32 ? (uint32_t)g.out_log : 64;
-  s.body_col = (uint32_t)g.body_col;
-  s.pre_rounded = g.mode == KsMode::Packing;
+  s.body_col = pf ? ~0u : (uint32_t)g.body_col;
+  s.pre_rounded = g.mode == KsMode::Packing || pf;
+  s.key_cols = pf ? (uint32_t)(g.out_size / g.n_keys) : s.out_size;
+  s.key_stride = (uint64_t)s.in_dim * g.level * s.key_cols;
   return s;
 }
 
@@ -455,7 +475,7 @@ size_t ks_key_bytes(const KsGeometry& g) {
 }
 
 size_t ks_digit_bytes(const KsGeometry& g, size_t batch) {
-  const size_t kb = (g.in_dim * (size_t)g.level * (size_t)ks_digit_bytes_per_term(g.base_log) + 63) / 64;
+  const size_t kb = ks_shape(g).KB;
   const size_t rows = (batch + 16 * ks::GM - 1) / (16 * ks::GM) * 16 * ks::GM;
   return rows * kb * 64;
 }

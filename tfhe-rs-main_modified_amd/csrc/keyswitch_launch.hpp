@@ -13,6 +13,9 @@ enum class KsMode {
   Ks32,     // keyswitch_lwe_ciphertext_with_scalar_change (:331-447): u32 key, 4 byte planes, u32 rows mod 2^out_log
   Packing,  // keyswitch_lwe_ciphertext_into_glwe_ciphertext (lwe_packing_keyswitch.rs:102-187): u64 key of (k+1) N
             // columns, digits of the pre-rounded mask, the body at column k N
+  Pfpks,    // private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext (lwe_private_functional_packing_
+            // keyswitch.rs:20-88) against a key list: in_dim + 1 blocks per key (the body word is decomposed like the
+            // mask, pre-rounded), n_keys (k+1) N columns, nothing added to the output
 };
 
 // The geometry of one prepared key: in_dim blocks of `level` rows of out_size words.
@@ -22,6 +25,7 @@ struct KsGeometry {
   int base_log = 0, level = 0;
   int out_log = 64;     // Ks32: the output modulus 2^out_log (1 <= out_log <= 32)
   size_t body_col = 0;  // the output column that receives the input body: out_size - 1, or k N when packing
+  size_t n_keys = 1;    // Pfpks: keys of the list, out_size / n_keys columns each (in_dim + 1 blocks of `level` rows)
 };
 
 // keyswitch.hip — the keyswitches on the int8 matrix cores.

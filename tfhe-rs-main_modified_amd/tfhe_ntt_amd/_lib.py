@@ -197,6 +197,20 @@ _SIGS = {
     "mi_glwe_compressed_words128": (_int, [_sz, _int, _sz, _int, ctypes.POINTER(_sz)]),
     "mi_glwe_compress128_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
     "mi_glwe_extract128_batch": (_int, [_vp, _vp, _sz, _int, _sz, _int, _sz, _int, _vp]),
+    "mi_lwe_pfpksk_list_create": (_int, [_vp, _sz, _sz, _int, _sz, _int, _int, _int, _vp, ctypes.POINTER(_vp)]),
+    "mi_lwe_pfpksk_list_destroy": (_int, [_vp]),
+    "mi_lwe_pfpksk_list_info": (_int, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_int),
+                                       ctypes.POINTER(_sz), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "mi_lwe_pfpks_batch": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "mi_fft64_ext_product_batch_indexed": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _int, _int, _int, _sz, _vp]),
+    "mi_fft64_cmux_batch_indexed": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _int, _int, _int, _sz, _vp]),
+    "mi_fft64_extract_bits_batch": (_int, [_vp, _vp, _vp, _vp, _int, _sz, _sz, _vp]),
+    "mi_fft64_circuit_bootstrap_boolean_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _int, _int, _int, _vp]),
+    "mi_fft64_cmux_tree_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _sz, _vp]),
+    "mi_fft64_wop_blind_rotate_batch": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _sz, _vp]),
+    "mi_fft64_vertical_packing_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _int, _int, _int, _sz, _vp]),
+    "mi_fft64_circuit_bootstrap_boolean_vertical_packing_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz,
+                                                                         _int, _int, _sz, _vp]),
 }
 
 

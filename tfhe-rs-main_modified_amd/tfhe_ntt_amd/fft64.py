@@ -110,36 +110,50 @@ def convert_standard_lwe_bootstrap_key_to_fourier(input_bsk, output_bsk, fft: Ff
                                     input_bsk.numel() // n, _stream(input_bsk)))
 
 
-def _ggsw_k(ggsw, level, n):
+def _ggsw_k(ggsw, level, n, allow_list=False):
     if ggsw.dim() < 5:
         raise ValueError(f"assertion failed: fourier ggsw shape {tuple(ggsw.shape)}")
     k = int(ggsw.shape[-4]) - 1
     want = (level, k + 1, k + 1, n // 2, 2)
-    if tuple(ggsw.shape[-5:]) != want or ggsw.numel() != level * (k + 1) ** 2 * n:
+    if tuple(ggsw.shape[-5:]) != want or (ggsw.numel() != level * (k + 1) ** 2 * n and not allow_list):
         raise ValueError(f"assertion failed: fourier ggsw shape {tuple(ggsw.shape)} != {want}")
     return k
 
 
-def _ext(fft, out, ggsw, glwe, base_log, level, cmux):
+def _ext(fft, out, ggsw, glwe, base_log, level, cmux, ggsw_index=None):
     n = fft.n
-    k = _ggsw_k(ggsw, level, n)
+    k = _ggsw_k(ggsw, level, n, ggsw_index is not None)
     if out.dim() < 2 or tuple(out.shape[-2:]) != (k + 1, n):
         raise ValueError(f"assertion failed: out shape {tuple(out.shape)} != (..., {k + 1}, {n})")
     if glwe.shape != out.shape:
         raise ValueError(f"assertion failed: glwe shape {tuple(glwe.shape)} != out shape {tuple(out.shape)}")
     b = out.numel() // ((k + 1) * n)
+    if ggsw_index is not None:
+        from .ntt64_pbs import _index
+        n_ggsw = ggsw.numel() // (level * (k + 1) ** 2 * n)
+        fn = lib().mi_fft64_cmux_batch_indexed if cmux else lib().mi_fft64_ext_product_batch_indexed
+        check(fn(fft.handle, _dev(out, "out"), _dev(glwe, "glwe"), _fdev(ggsw, "ggsw"),
+                 _index(ggsw_index, b, out.device, "ggsw_index"), n_ggsw, k, base_log, level, b, _stream(out)))
+        return
     fn = lib().mi_fft64_cmux_batch if cmux else lib().mi_fft64_ext_product_batch
     check(fn(fft.handle, _dev(out, "out"), _dev(glwe, "glwe"), _fdev(ggsw, "ggsw"), k, base_log, level, b, _stream(out)))
 
 
-def add_external_product_assign(out, ggsw, glwe, base_log: int, level: int, fft: Fft | None = None) -> None:
-    """out += ggsw (.) glwe (native 2^64 GLWEs, Fourier GGSW (level, k+1, k+1, N/2, 2))."""
-    _ext(fft or Fft(int(out.shape[-1]), out.device.index or 0), out, ggsw, glwe, base_log, level, False)
+def add_external_product_assign(out, ggsw, glwe, base_log: int, level: int, fft: Fft | None = None,
+                                ggsw_index=None) -> None:
+    """out += ggsw (.) glwe (native 2^64 GLWEs, Fourier GGSW (level, k+1, k+1, N/2, 2)).  With ``ggsw_index`` (int32
+    device tensor, one entry per item) ``ggsw`` is a list (n_ggsw, level, k+1, k+1, N/2, 2) and item b multiplies by
+    ``ggsw[ggsw_index[b]]``; an out-of-range index leaves the item untouched."""
+    _ext(fft or Fft(int(out.shape[-1]), out.device.index or 0), out, ggsw, glwe, base_log, level, False, ggsw_index)
 
 
-def cmux_assign(ct0, ct1, ggsw, base_log: int, level: int, fft: Fft | None = None) -> None:
-    """ct0 = cmux(ggsw, ct0, ct1); like the reference, ct1 is left holding ct1 - ct0."""
-    _ext(fft or Fft(int(ct0.shape[-1]), ct0.device.index or 0), ct0, ggsw, ct1, base_log, level, True)
+def cmux_assign(ct0, ct1, ggsw, base_log: int, level: int, fft: Fft | None = None, ggsw_index=None) -> None:
+    """ct0 = cmux(ggsw, ct0, ct1); like the reference, ct1 is left holding ct1 - ct0.  ``ggsw_index``: one GGSW of
+    the list per item, as ``add_external_product_assign`` (an out-of-range index leaves ct0 and ct1 untouched)."""
+    _ext(fft or Fft(int(ct0.shape[-1]), ct0.device.index or 0), ct0, ggsw, ct1, base_log, level, True, ggsw_index)
+
+
+cmux = cmux_assign
 
 
 class FourierLweBootstrapKey:
@@ -366,7 +380,7 @@ def multi_bit_blind_rotate_assign(lwe_in, lut, key: FourierLweMultiBitBootstrapK
 
 
 __all__ = ["Fft", "FourierLweBootstrapKey", "convert_standard_lwe_bootstrap_key_to_fourier",
-           "add_external_product_assign", "cmux_assign", "programmable_bootstrap_lwe_ciphertext",
+           "add_external_product_assign", "cmux_assign", "cmux", "programmable_bootstrap_lwe_ciphertext",
            "batch_programmable_bootstrap_lwe_ciphertext", "blind_rotate_assign",
            "FourierLweMultiBitBootstrapKey", "convert_standard_lwe_multi_bit_bootstrap_key_to_fourier",
            "multi_bit_programmable_bootstrap_lwe_ciphertext", "batch_multi_bit_programmable_bootstrap_lwe_ciphertext",

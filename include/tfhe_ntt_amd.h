@@ -925,8 +925,12 @@ int mi_fft64_circuit_bootstrap_boolean_batch(const mi_fft64_pbs_key *bsk, const 
                                              double *ggsw_fourier_out, const uint64_t *lwe_in, size_t batch,
                                              int delta_log, int base_log_cbs, int level_cbs, void *stream);
 /* The GGSW lists of the three calls below: batch x ggsw_stride Fourier GGSWs, item b's at b * ggsw_stride; a call
- * reads GGSWs [ggsw_first, ggsw_first + count) of each item (batch * ggsw_stride < 2^32).  Every item evaluates
- * n_outputs functions with the same GGSWs.
+ * reads GGSWs [ggsw_first, ggsw_first + count) of each item (batch * ggsw_stride < 2^32) and nothing of the others,
+ * so the result equals the call on the contiguous list of those GGSWs alone (ggsw_stride = count, ggsw_first = 0), bit
+ * for bit.  count is r for the tree and n_rot for the rotation; ggsw_first + count > ggsw_stride is
+ * MI_ERR_INVALID_ARG ("the GGSW range exceeds the GGSWs of an item"), checked before any buffer is read; count = 0 with
+ * ggsw_first = ggsw_stride is the empty range at the item's end.  Every item evaluates n_outputs functions with the
+ * same GGSWs.
  *
  * cmux_tree_memory_optimized (:459-583): lut_polys holds n_outputs x n_polys polynomials (N u64, shared by the batch),
  * n_polys = 2^r (else MI_ERR_INVALID_ARG); glwe_out[b * n_outputs + o] = the tree over output o's polynomials as trivial

@@ -66,6 +66,26 @@ def test_wop_restatement_decodes_add_one():
     assert W.decode_output(out[:, 0], ks["big_sk"]) == [(m + 1) % 1024 for m in msgs]
 
 
+def test_restatement_selects_every_leaf_by_encrypted_bits():
+    """Shape A, r = 4: for every m < 16, m's bits encrypted at delta_log 63, circuit-bootstrapped, then the CMUX tree
+    over W.leaf_lut; all N coefficients of item m decode to leaf m at 4 bits (margin 2^59).  At r >= 3 the bit-reversed
+    and the natural leaf order differ in more than a swap.  Measured: worst absolute error 2^42.7 here, 2^43.1 at
+    SHAPE_N512 with r = 3 (about 9 s on the host, so only tests/test_wopbs_corners_gpu.py runs that shape)."""
+    import fft_oracle as F
+
+    shape, r = W.SHAPE_A, 4
+    ks = W.keys(shape)
+    fbsk = F.forward_as_torus(ks["bsk"])
+    ggsw = W.circuit_bootstrap_ref(W.leaf_selector_lwes(shape, r), fbsk, *shape.pbs, shape.k, shape.N, ks["pfpksk"],
+                                   *shape.pfks, 63, *shape.cbs)
+    fggsw = F.forward_as_torus(ggsw).reshape((1 << r, r) + ggsw.shape[1:-1] + (shape.N // 2,))
+    lut = W.leaf_lut(r, shape.N)
+    assert len({tuple(row >> np.uint64(60)) for row in lut}) == 1 << r  # the leaves are distinct
+    got, err = W.decode_leaves(W.cmux_tree_ref(lut, fggsw, *shape.cbs, shape.k), ks["glwe_sk"])
+    print(f"\nleaf selection {shape.name} r={r}: numpy worst error 2^{np.log2(max(err, 1)):.1f}", end="")
+    assert np.array_equal(got, lut >> np.uint64(60))
+
+
 _DIM = "lwe dimension out of range"
 _POW2, _GLWE = "polynomial size must be a power of two", "glwe size out of range"
 _KEYS = "n_keys * (glwe_dim + 1) * polynomial_size must be in [1, 2^24)"

@@ -287,6 +287,34 @@ def decode_output(ct, big_sk, n_bits=N_INPUT_BITS):
         return [int(v) for v in ((pt + U64(1 << (63 - n_bits))) >> U64(64 - n_bits))]
 
 
+LEAF_BITS = 4  # every leaf of the selection case carries a 4-bit message: half a step is 2^59
+
+
+def leaf_lut(r, n):
+    """(2^r, N): lut[p][c] = ((7 p + c) mod 16) << 60; any two leaves differ in every coefficient while r <= 4."""
+    p, c = np.arange(1 << r, dtype=U64)[:, None], np.arange(n, dtype=U64)[None, :]
+    return ((U64(7) * p + c) % U64(1 << LEAF_BITS)) << U64(64 - LEAF_BITS)
+
+
+def leaf_selector_lwes(shape, r):
+    """For every m < 2^r its r bits, most significant first, encrypted at delta_log 63 under the small key:
+    (2^r * r, n + 1), item m's bits in rows m r .. m r + r - 1.  The tree's last GGSW selects the first layer, so these
+    bits select leaf m."""
+    bits = [((m >> (r - 1 - j)) & 1) << 63 for m in range(1 << r) for j in range(r)]
+    return H.lwe_encrypt_batch(H.rng(shape.seed + 2000 + r), bits, keys(shape)["small_sk"], shape.noise_log2)
+
+
+def decode_leaves(glwe, glwe_sk):
+    """glwe (2^r, k+1, N) -> what each coefficient decodes to at LEAF_BITS bits, (2^r, N), and the largest absolute
+    error against leaf m for item m."""
+    r = glwe.shape[0].bit_length() - 1
+    lut = leaf_lut(r, glwe.shape[-1])
+    pt = np.stack([H.glwe_decrypt(g, glwe_sk) for g in glwe])
+    with np.errstate(over="ignore"):
+        err = int(np.abs((pt - lut).view(np.int64)).max())
+        return (pt + U64(1 << (63 - LEAF_BITS))) >> U64(64 - LEAF_BITS), err
+
+
 def wop_ref(shape, lwe_in, luts_per_output, n_bits=N_INPUT_BITS):
     """Extract bits, circuit bootstrap every bit at delta_log 63, vertical packing of every output's LUT:
     (batch, k N + 1) -> (batch, n_outputs, k N + 1), and the extracted bits."""

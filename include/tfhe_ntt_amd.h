@@ -964,6 +964,101 @@ int mi_fft64_circuit_bootstrap_boolean_vertical_packing_batch(
     const uint64_t *lwe_list_in, size_t n_bits, const uint64_t *big_lut, size_t n_polys, size_t n_outputs,
     int base_log_cbs, int level_cbs, size_t batch, void *stream);
 
+/* ---- LWE linear algebra with gather (core_crypto/algorithms/lwe_linear_algebra.rs) -----------------------------
+ * lwe_out[i] = sum_t coeff[i * terms + t] * lwe_in[index[i * terms + t]] + (0, ..., 0, plaintext[i]) for i < n_out, on
+ * rows of lwe_dim + 1 u64, native modulus with wrapping u64 arithmetic.  A term whose index is >= n_in contributes
+ * nothing (ragged term counts, trivial ciphertexts); terms = 0 gives the trivial ciphertexts of `plaintext` (lwe_in is
+ * not read).  index (u32) and coeff (i64) are device arrays of n_out * terms entries; coeff NULL: every coefficient 1;
+ * plaintext: device array of n_out u64 or NULL (nothing added).  With the right index and coefficients this one call
+ * is lwe_ciphertext_add[_assign] (:67, :190), lwe_ciphertext_sub[_assign] (:702, :789), lwe_ciphertext_opposite_assign
+ * (:490), lwe_ciphertext_cleartext_mul[_assign] (:555, :624), lwe_ciphertext_plaintext_add_assign (:275) and
+ * _plaintext_sub_assign (:383), shortint's bivariate packing lhs * factor + rhs (shortint/server_key/
+ * bivariate_pbs.rs:152-167), and the gather / scatter of the CUDA backend's lwe_indexes_in / lwe_indexes_out
+ * (backends/tfhe-cuda-backend/cuda/include/pbs/programmable_bootstrap.h).  Device pointers on `device`, async on
+ * `stream`; n_out = 0 is MI_OK; lwe_out overlapping lwe_in is MI_ERR_INVALID_ARG ("lwe_out overlaps lwe_in"), as are
+ * lwe_dim outside [1, 2^24), n_in or n_out >= 2^31 and terms >= 2^16. */
+int mi_lwe_linear_combination_batch(uint64_t *lwe_out, const uint64_t *lwe_in, size_t lwe_dim, size_t n_in,
+                                    size_t n_out, size_t terms, const uint32_t *index, const int64_t *coeff,
+                                    const uint64_t *plaintext, int device, void *stream);
+
+/* ---- shortint: lookup tables and the KS -> MS -> PBS atomic pattern --------------------------------------------
+ * Reference paths relative to tfhe/src/shortint.  A mi_shortint_key bundles what shortint::ServerKey holds for the
+ * KS-PBS order (server_key/mod.rs, atomic_pattern/standard.rs): borrowed handles (the caller keeps them alive) of a
+ * keyswitch key k N -> n, one bootstrap key of `pbs_engine` (mi_pbs_ntt64_key of the BNF variant, mi_fft64_pbs_key or
+ * mi_fft64_multi_bit_pbs_key, passed as const void *) and, optionally, a mi_ms_noise_key (ModulusSwitchConfiguration::
+ * DriftTechniqueNoiseReduction); the modulus switch of the bootstrap (MI_MS_STANDARD or MI_MS_CENTERED); and
+ * message_modulus / carry_modulus.  It owns the five lookup tables of the radix calls below (uploaded with a blocking
+ * copy at creation).
+ * mi_shortint_key_check states the argument rules on plain numbers, the first failing rule answering:
+ * MI_ERR_INVALID_ARG "unknown pbs engine"; MI_ERR_UNSUPPORTED for a Solinas-variant NTT key (its input is not a native
+ * LWE); MI_ERR_INVALID_ARG for ksk out_dim != the bootstrap key's n_lwe, ksk in_dim != k N, moduli that are not powers
+ * of two or with message_modulus * carry_modulus > N / 2, an ms_mode other than the two above, an ms-noise key together
+ * with the multi-bit engine, a centered switch with the multi-bit engine or with an ms-noise key (both end in the
+ * standard switch), an ms-noise key of another dimension than n.  mi_shortint_key_create answers "out_key is NULL",
+ * "key is NULL", then those rules read off its handles. */
+typedef enum mi_shortint_pbs_engine {
+    MI_SHORTINT_PBS_NTT64 = 0,
+    MI_SHORTINT_PBS_FFT64 = 1,
+    MI_SHORTINT_PBS_FFT64_MULTI_BIT = 2
+} mi_shortint_pbs_engine;
+typedef struct mi_shortint_key mi_shortint_key;
+int mi_shortint_key_check(size_t ksk_in_dim, size_t ksk_out_dim, size_t pbs_n_lwe, int k, size_t polynomial_size,
+                          int pbs_engine, int ntt_variant, int has_ms_noise, size_t ms_noise_lwe_dim, int ms_mode,
+                          uint64_t message_modulus, uint64_t carry_modulus);
+int mi_shortint_key_create(const mi_lwe_ksk *ksk, int pbs_engine, const void *pbs_key, const mi_ms_noise_key *ms_noise,
+                           int ms_mode, uint64_t message_modulus, uint64_t carry_modulus, mi_shortint_key **out_key);
+int mi_shortint_key_destroy(mi_shortint_key *key);
+int mi_shortint_key_info(const mi_shortint_key *key, int *pbs_engine, int *ms_mode, int *has_ms_noise,
+                         uint64_t *message_modulus, uint64_t *carry_modulus, size_t *big_lwe_dim,
+                         size_t *small_lwe_dim);
+/* fill_accumulator_with_encoding (engine/mod.rs:80-141), a host function: glwe_host ((k + 1) N u64) gets a zero mask
+ * and the body of boxes of N / (m c) coefficients, box i holding table[i] * (2^63 / (m c)) (wrapping), the first half
+ * box negated and the whole rotated left by half a box.  table_len must be m c.  The caller evaluates the function:
+ * table[i] = f(i) is generate_lookup_table (server_key/mod.rs:805, :1649), table[i] = f((i / m) % m, i % m) is
+ * generate_lookup_table_bivariate_with_factor at factor m (server_key/bivariate_pbs.rs:57-108). */
+int mi_shortint_lut_fill(uint64_t *glwe_host, size_t polynomial_size, int k, uint64_t message_modulus,
+                         uint64_t carry_modulus, const uint64_t *table, size_t table_len);
+/* apply_lookup_table (server_key/mod.rs:935-960), apply_programmable_bootstrap (:1542), message_extract
+ * (:1189), carry_extract (:1111) and, after one packing call to mi_lwe_linear_combination_batch, unchecked_apply_lookup_table_bivariate
+ * (server_key/bivariate_pbs.rs:141-190), batched: lwe_in holds n_in LWEs of k N + 1 u64, lwe_out n_items.  The sequence:
+ * mi_lwe_keyswitch_batch of all n_in inputs; with an ms-noise key mi_lwe_ms_noise_improve_and_switch_batch at
+ * log2(2 N), the bootstrap then running MI_MS_PRE_SWITCHED; with in_index (device u32, n_items entries) the gather
+ * mi_lwe_linear_combination_batch of the small LWEs, item j taking input in_index[j] (one input may feed several lookup
+ * tables for one keyswitch), without it n_items must equal n_in; the engine's *_pbs_batch_lut_indexed with lut_list
+ * (n_lut GLWEs) and lut_index (device u32; NULL: item j uses GLWE j).  An item with in_index >= n_in or lut_index >=
+ * n_lut is left untouched.  lwe_out == lwe_in is the reference's _assign form; a partial overlap is
+ * MI_ERR_INVALID_ARG.  Async on `stream`, stream-ordered scratch. */
+int mi_shortint_apply_lut_batch(const mi_shortint_key *key, uint64_t *lwe_out, const uint64_t *lwe_in, size_t n_in,
+                                const uint32_t *in_index, const uint64_t *lut_list, const uint32_t *lut_index,
+                                size_t n_lut, size_t n_items, void *stream);
+
+/* ---- Radix integers (tfhe/src/integer) --------------------------------------------------------------------------
+ * A radix batch is n_integers x n_blocks LWEs of k N + 1 u64, the least significant block first.  All three calls are
+ * in place on device memory, async on `stream`, and fixed sequences of mi_lwe_linear_combination_batch and
+ * mi_shortint_apply_lut_batch (written out at the top of csrc/c_api_shortint.cpp); n_integers = 0 is MI_OK, n_blocks =
+ * 0 MI_ERR_INVALID_ARG.
+ * mi_radix_propagate_single_carry_batch: blocks of value <= 2 (m - 1) -> blocks < m, the Hillis-Steele prefix scan of
+ * compute_prefix_sum_hillis_steele (integer/server_key/radix_parallel/add.rs:1452-1487) as the CUDA backend's
+ * host_propagate_single_carry runs it (backends/tfhe-cuda-backend/cuda/src/integer/integer.cuh).  Round 1: one
+ * keyswitch per block and two lookup tables, the message x mod m and the state NONE 0 / GENERATED 1 (x >= m) /
+ * PROPAGATED 2 (x = m - 1; never for block 0); ceil(log2 n_blocks) scan rounds, round r combining block i >= 2^r with
+ * block i - 2^r through one bivariate table on m * cur + prev (cur = PROPAGATED takes prev); a last round (message_i
+ * + carry_{i-1}) mod m: 2 + ceil(log2 n_blocks) bootstrap rounds, one at n_blocks = 1.  carry_out (n_integers LWEs, or
+ * NULL) receives the carry out of the top block.  MI_ERR_UNSUPPORTED unless m c >= 16, c <= m and 2 m + 2 < m c (the
+ * packed scan operand has to stay under the padding bit), for n_blocks > 1.
+ * mi_radix_full_propagate_batch (full_propagate_parallelized, radix_parallel/mod.rs:228; partial_propagate :91-201): blocks of any value
+ * < m c.  One round of message_extract and carry_extract on every block, each carry added into the next block, then the
+ * single-carry propagation (:140-158); where that is unsupported, the extract-and-add round n_blocks - 1 more times,
+ * which ends in the blocks of the sequential loop (:187-199).
+ * mi_radix_add_batch: radix_out = lhs + rhs blockwise (radix_out may be lhs or rhs), then the single-carry propagation:
+ * add_parallelized on clean inputs (radix_parallel/add.rs), and with carry_out unsigned_overflowing_add_parallelized. */
+int mi_radix_propagate_single_carry_batch(const mi_shortint_key *key, uint64_t *radix, uint64_t *carry_out,
+                                          size_t n_blocks, size_t n_integers, void *stream);
+int mi_radix_full_propagate_batch(const mi_shortint_key *key, uint64_t *radix, size_t n_blocks, size_t n_integers,
+                                  void *stream);
+int mi_radix_add_batch(const mi_shortint_key *key, uint64_t *radix_out, const uint64_t *lhs, const uint64_t *rhs,
+                       uint64_t *carry_out, size_t n_blocks, size_t n_integers, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

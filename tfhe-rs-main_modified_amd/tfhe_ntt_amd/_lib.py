@@ -211,6 +211,18 @@ _SIGS = {
     "mi_fft64_vertical_packing_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _int, _int, _int, _sz, _vp]),
     "mi_fft64_circuit_bootstrap_boolean_vertical_packing_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz,
                                                                          _int, _int, _sz, _vp]),
+    "mi_lwe_linear_combination_batch": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _int, _vp]),
+    "mi_shortint_key_check": (_int, [_sz, _sz, _sz, _int, _sz, _int, _int, _int, _sz, _int, _u64, _u64]),
+    "mi_shortint_key_create": (_int, [_vp, _int, _vp, _vp, _int, _u64, _u64, ctypes.POINTER(_vp)]),
+    "mi_shortint_key_destroy": (_int, [_vp]),
+    "mi_shortint_key_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                    ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_sz),
+                                    ctypes.POINTER(_sz)]),
+    "mi_shortint_lut_fill": (_int, [_p64, _sz, _int, _u64, _u64, _p64, _sz]),
+    "mi_shortint_apply_lut_batch": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "mi_radix_propagate_single_carry_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "mi_radix_full_propagate_batch": (_int, [_vp, _vp, _sz, _sz, _vp]),
+    "mi_radix_add_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
 }
 
 

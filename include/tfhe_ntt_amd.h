@@ -1051,7 +1051,9 @@ int mi_shortint_apply_lut_batch(const mi_shortint_key *key, uint64_t *lwe_out, c
  * single-carry propagation (:140-158); where that is unsupported, the extract-and-add round n_blocks - 1 more times,
  * which ends in the blocks of the sequential loop (:187-199).
  * mi_radix_add_batch: radix_out = lhs + rhs blockwise (radix_out may be lhs or rhs), then the single-carry propagation:
- * add_parallelized on clean inputs (radix_parallel/add.rs), and with carry_out unsigned_overflowing_add_parallelized. */
+ * add_parallelized on clean inputs (radix_parallel/add.rs), and with carry_out unsigned_overflowing_add_parallelized.
+ * carry_out (n_integers LWEs) is written last and is disjoint from every other buffer of the call: one that overlaps
+ * radix (propagation), or radix_out, lhs or rhs (addition), is MI_ERR_INVALID_ARG before any device call. */
 int mi_radix_propagate_single_carry_batch(const mi_shortint_key *key, uint64_t *radix, uint64_t *carry_out,
                                           size_t n_blocks, size_t n_integers, void *stream);
 int mi_radix_full_propagate_batch(const mi_shortint_key *key, uint64_t *radix, size_t n_blocks, size_t n_integers,

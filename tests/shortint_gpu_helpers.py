@@ -36,44 +36,52 @@ def i32(values):
 
 
 class KeySet:
-    """The three bootstrap keys of one (N, n) shape over one small secret key, a keyswitch key and the drift key."""
+    """The three bootstrap keys of one (N, k, n) shape over one small secret key, a keyswitch key and the drift key.
+    ``device=False`` stops after the host words (the CPU noise measurement needs no more)."""
 
-    def __init__(self, engine, oracle, n, small, real, seed):
-        import torch
-        M, X, KS, NR = engine.ntt64_pbs, engine.fft64, engine.lwe_keyswitch, engine.modulus_switch_noise_reduction
+    def __init__(self, engine, oracle, n, small, real, seed, k=1, ks_level=KS_L, device=True):
         g = H.rng(seed)
-        self.n, self.small, self.k, self.real = n, small, 1, real
-        self.size = n + 1
+        self.n, self.small, self.k, self.real, self.ks_l = n, small, k, real, ks_level
+        self.size = k * n + 1
         if real:
+            assert k == 1, "the real key generation is the k = 1 one"
             glwe_sk = H.binary_key(g, (1, n))
             self.big_sk, self.small_sk = H.glwe_sk_as_lwe_sk(glwe_sk), H.binary_key(g, small)
-            self.ksk_words = H.ksk_gen(g, self.big_sk, self.small_sk, KS_BL, KS_L, noise_log2=12)
+            self.ksk_words = H.ksk_gen(g, self.big_sk, self.small_sk, KS_BL, ks_level, noise_log2=12)
             bsk_std = H.bsk_gen_native_l1(g, self.small_sk, glwe_sk, PBS_BL, 10)
-            mb_std = MB.multi_bit_bsk_gen(g, oracle, self.small_sk, glwe_sk, PBS_BL, PBS_L, 10, 2)
+            mb_std = MB.multi_bit_bsk_gen(g, oracle, self.small_sk, glwe_sk, PBS_BL, PBS_L, 10, 2) if n == 2048 else None
             self.zeros_words = H.lwe_encrypt_batch(g, np.zeros(32, np.uint64), self.small_sk, 12)
         else:
-            self.ksk_words = H.uniform_u64(g, (n, KS_L, small + 1))
-            bsk_std = H.uniform_u64(g, (small, PBS_L, 2, 2, n))
-            mb_std = H.uniform_u64(g, (small // 2, 4, PBS_L, 2, 2, n))
+            self.ksk_words = H.uniform_u64(g, (k * n, ks_level, small + 1))
+            bsk_std = H.uniform_u64(g, (small, PBS_L, k + 1, k + 1, n))
+            mb_std = H.uniform_u64(g, (small // 2, 4, PBS_L, k + 1, k + 1, n))
             self.zeros_words = H.uniform_u64(g, (16, small + 1))
-        self.plan = engine.Plan.try_new(n, engine.SOLINAS_P)
-        self.bsk_ntt = oracle.NttContext(n).bsk_to_ntt(bsk_std, 64, False)  # Raw: what the oracle's BNF PBS reads
+            mb_std = mb_std if n == 2048 else None
         self.ctx = oracle.NttContext(n)
+        self.bsk_ntt = self.ctx.bsk_to_ntt(bsk_std, 64, False)  # Raw: what the oracle's BNF PBS reads
+        # a bound that some ciphertexts meet and some do not, so that the drift step does add candidates
+        self.ms_params = (2.0**52 * 1.5 if real else 2.0**53 * 1.2, 1.0, 0.0)
+        self._server = {}
+        self.engine = engine
+        if device:
+            self._to_device(bsk_std, mb_std)
+
+    def _to_device(self, bsk_std, mb_std):
+        import torch
+        engine, n = self.engine, self.n
+        M, X, KS, NR = engine.ntt64_pbs, engine.fft64, engine.lwe_keyswitch, engine.modulus_switch_noise_reduction
+        self.plan = engine.Plan.try_new(n, engine.SOLINAS_P)
         self._bsk_dev = dev(self.bsk_ntt)
         fb = torch.zeros(bsk_std.shape[:-1] + (n // 2, 2), dtype=torch.float64, device="cuda")
         X.convert_standard_lwe_bootstrap_key_to_fourier(dev(bsk_std), fb)
         self.pbs = {"ntt": M.NttBootstrapKey(self.plan, self._bsk_dev, PBS_BL, PBS_L, M.BNF),
                     "fft": X.FourierLweBootstrapKey(fb, PBS_BL, PBS_L)}
-        if n == 2048:  # the multi-bit engine's one polynomial size
+        if mb_std is not None:  # N = 2048, the multi-bit engine's one polynomial size
             fm = torch.zeros(mb_std.shape[:-1] + (n // 2, 2), dtype=torch.float64, device="cuda")
             X.convert_standard_lwe_multi_bit_bootstrap_key_to_fourier(dev(mb_std), fm)
             self.pbs["multi-bit"] = X.FourierLweMultiBitBootstrapKey(fm, PBS_BL, PBS_L, 2)
-        self.ksk = KS.LweKeyswitchKey(dev(self.ksk_words), KS_BL, KS_L)
-        # a bound that some ciphertexts meet and some do not, so that the drift step does add candidates
-        self.ms_params = (2.0**52 * 1.5 if real else 2.0**53 * 1.2, 1.0, 0.0)
+        self.ksk = KS.LweKeyswitchKey(dev(self.ksk_words), KS_BL, self.ks_l)
         self.msk = NR.ModulusSwitchNoiseReductionKey(dev(self.zeros_words), *self.ms_params)
-        self._server = {}
-        self.engine = engine
 
     def server(self, which, drift=False, ms_mode=0, m=MSG, c=CARRY):
         key = (which, drift, ms_mode, m, c)
@@ -83,12 +91,59 @@ class KeySet:
         return self._server[key]
 
 
-def key_set(engine, oracle, name):
-    """"real": N = 2048, n = 64 under real keys; "u1024" / "u2048": uniform key words at n = 16 for the bit-exact tests."""
+# name: (N, n, real, seed, k, keyswitch levels)
+SETS = {"real": (2048, 64, True, 0x51a0, 1, KS_L), "u1024": (1024, 16, False, 0x51a1, 1, KS_L),
+        "u2048": (2048, 16, False, 0x51a2, 1, KS_L), "u1024k2": (1024, 16, False, 0x51a3, 2, KS_L),
+        "u2048k2": (2048, 16, False, 0x51a4, 2, KS_L), "u8192": (8192, 16, False, 0x51a5, 1, KS_L),
+        "real4096": (4096, 64, True, 0x51a7, 1, 6), "real2048n16": (2048, 16, True, 0x51a8, 1, 6)}
+# The real set that meets the noise condition of tests/test_shortint_corners_gpu.py at each (m, c), for the NTT and
+# f64 engines; the multi-bit engine has N = 2048 only and takes REAL_MULTI_BIT_8_8 at (8, 8).
+REAL_FOR = {(4, 4): "real", (8, 4): "real", (4, 8): "real", (2, 2): "real", (8, 8): "real4096"}
+REAL_MULTI_BIT_8_8 = "real2048n16"
+
+
+def key_set(engine, oracle, name, device=True):
+    """"real": N = 2048, n = 64 under real keys, keyswitch 2^4 x 4; "real4096": N = 4096, n = 64, keyswitch 2^4 x 6;
+    "real2048n16": N = 2048, n = 16, keyswitch 2^4 x 6; "u<N>[k2]": uniform key words at n = 16 (k = 1, or 2 with
+    the suffix) for the bit-exact tests.  device=False: the host words only, made again at every call."""
+    if not device:
+        return KeySet(engine, oracle, *SETS[name], device=False)
     if name not in _sets:
-        args = {"real": (2048, 64, True, 0x51a0), "u1024": (1024, 16, False, 0x51a1), "u2048": (2048, 16, False, 0x51a2)}
-        _sets[name] = KeySet(engine, oracle, *args[name])
+        _sets[name] = KeySet(engine, oracle, *SETS[name])
     return _sets[name]
+
+
+SENTINEL = np.uint64(0x5E5E5E5E5E5E5E5E)
+
+
+def oracle_apply(oracle, ks, lwe, luts, lut_index, in_index, mode, drift, ms_params=None, k=1):
+    """mi_shortint_apply_lut_batch through oracle.lwe_keyswitch and the oracle's PBS at GLWE dimension k: the expected
+    output rows (SENTINEL where nothing is written), and which rows are written at all."""
+    import ms_noise_helpers as MN
+    n, small = ks.n, ks.small
+    cur = oracle.lwe_keyswitch(ks.ksk_words, lwe, small, KS_BL, ks.ks_l)
+    ms = mode
+    if drift:
+        log2n = (2 * n).bit_length() - 1
+        p = MN.Params(*(ms_params or ks.ms_params), log2n)
+        cand, _ = MN.choose_np(cur, ks.zeros_words, p)
+        cur, ms = MN.switch_np(MN.improve_np(cur, ks.zeros_words, cand), log2n), 2
+    n_items = len(lut_index)
+    src = np.arange(n_items) if in_index is None else np.asarray(in_index)
+    live = (src < lwe.shape[0]) & (np.asarray(lut_index) < luts.shape[0])
+    out = np.full((n_items, k * n + 1), SENTINEL, np.uint64)
+    rows = np.flatnonzero(live)
+    if rows.size:
+        if ms == 2:
+            acc = luts[np.asarray(lut_index)[rows]]
+            rot = ks.ctx.blind_rotate_batch(acc, cur[src[rows]], ks.bsk_ntt, k, PBS_BL, PBS_L, bnf=True, ms_mode=2)
+            out[rows] = np.stack([oracle.sample_extract(r, n, k) for r in rot])
+        else:
+            for l in set(np.asarray(lut_index)[rows].tolist()):
+                sel = rows[np.asarray(lut_index)[rows] == l]
+                out[sel] = ks.ctx.pbs_batch_bnf(cur[src[sel]], luts[l], ks.bsk_ntt, k, PBS_BL, PBS_L,
+                                                centered=(ms == 1))
+    return out, live
 
 
 # ---- the written sequences (public calls only) ----
@@ -215,22 +270,59 @@ def seq_add(engine, sk, out, lhs, rhs, carry_out=None):
 
 # ---- radix integers under the real key set ----
 
-def encrypt_blocks(ks, g, values):
+def delta_of(m=MSG, c=CARRY):
+    return (1 << 63) // (m * c)
+
+
+def encrypt_blocks(ks, g, values, m=MSG, c=CARRY):
     """values (...,) block values -> LWEs (..., size) under the big key, noise 2^10."""
     v = np.asarray(values, dtype=np.uint64)
-    cts = H.lwe_encrypt_batch(g, v.reshape(-1) * np.uint64(DELTA), ks.big_sk, noise_log2=10)
+    cts = H.lwe_encrypt_batch(g, v.reshape(-1) * np.uint64(delta_of(m, c)), ks.big_sk, noise_log2=10)
     return cts.reshape(v.shape + (ks.size,))
 
 
-def decrypt_blocks(ks, cts):
+def decrypt_blocks(ks, cts, m=MSG, c=CARRY):
     """LWEs (..., size) -> block values mod 2 m c (the padding bit kept, so that an overflow shows)."""
     dec = H.lwe_decrypt_batch(np.asarray(cts, dtype=np.uint64), ks.big_sk)
-    return np.vectorize(lambda d: H.decode(int(d), DELTA, MSG * CARRY))(dec)
+    return np.vectorize(lambda d: H.decode(int(d), delta_of(m, c), m * c))(dec)
 
 
-def radix_digits(values, blocks, m=MSG):
+def phase_errors(cts, sk, values, m=MSG, c=CARRY):
+    """The signed phase errors of LWEs (..., dim + 1) that should hold values * 2^63 / (m c) under sk."""
+    dec = H.lwe_decrypt_batch(np.asarray(cts, dtype=np.uint64), sk)
+    with np.errstate(over="ignore"):
+        return (dec - np.asarray(values, dtype=np.uint64) * np.uint64(delta_of(m, c))).view(np.int64)
+
+
+def radix_digits(values, blocks, m=MSG, c=CARRY):
     return np.array([[(int(v) // m**b) % m for b in range(blocks)] for v in values], dtype=np.uint64)
 
 
-def radix_values(digits, m=MSG):
+def radix_values(digits, m=MSG, c=CARRY):
     return [sum(int(x) * m**i for i, x in enumerate(row)) for row in digits]
+
+
+def measure_noise(oracle, ks, m, c, seed, multi_bit=False):
+    """Every value 0 .. m c - 1 through oracle.lwe_keyswitch, the standard modulus switch to 2 N and the oracle's
+    bootstrap through the identity table, under the real keys of ks, on the host -> the worst absolute phase error of
+    the keyswitched-and-switched input (under the small key) and of the output (under the big key).  multi_bit: the
+    input error is that of the multi-bit engine's switch at grouping factor 2 (multi_bit_helpers.group_degrees: one
+    rounding per group, of the sum of the mask elements the group's key bits select)."""
+    import shortint_ref as R
+    values = np.arange(m * c, dtype=np.uint64)
+    cts = encrypt_blocks(ks, H.rng(seed), values, m, c)
+    small = oracle.lwe_keyswitch(ks.ksk_words, cts, ks.small, KS_BL, ks.ks_l)
+    log2n = (2 * ks.n).bit_length() - 1
+    up = np.uint64(64 - log2n)
+    if multi_bit:
+        deg = MB.group_degrees(small[:, :-1].reshape(len(values), ks.small // 2, 2), 2, log2n)  # (items, groups, 4)
+        pick = (2 * ks.small_sk[0::2] + ks.small_sk[1::2]).astype(np.int64)  # the GGSW whose selection bits are the key's
+        mask = np.take_along_axis(deg, pick[None, :, None], axis=2)[:, :, 0].sum(axis=1)
+        body = oracle.lwe_ms64(small, log2n, False)[:, -1].astype(np.int64)
+        with np.errstate(over="ignore"):
+            phase = ((body - mask) % (1 << log2n)).astype(np.uint64) << up
+            e_in = (phase - values * np.uint64(delta_of(m, c))).view(np.int64)
+    else:
+        e_in = phase_errors(oracle.lwe_ms64(small, log2n, False) << up, ks.small_sk, values, m, c)
+    out = ks.ctx.pbs_batch_bnf(small, R.lut_fill(ks.n, 1, m, c, list(range(m * c))), ks.bsk_ntt, 1, PBS_BL, PBS_L)
+    return int(np.abs(e_in).max()), int(np.abs(phase_errors(out, ks.big_sk, values, m, c)).max())

@@ -161,3 +161,60 @@ def test_key_create_rejections_on_real_handles(engine):
     eight_two = S.ShortintServerKey(ksk, bnf, 8, 2)
     answered(L().mi_radix_propagate_single_carry_batch(eight_two._h, p, None, 2, 1, None), UNSUPPORTED, "single carry")
     torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_carry_out_overlap_is_rejected(engine):
+    """carry_out is written after radix / radix_out: one that overlaps the radix, the output or an operand (its first
+    row, its last row, the same address, one word) is MI_ERR_INVALID_ARG before any device call (the buffers keep their
+    words); a disjoint carry_out in the same tensor, on either side, is accepted and gives what a separate tensor gives."""
+    import torch
+    M, KS, S = engine.ntt64_pbs, engine.lwe_keyswitch, engine.shortint
+    n, small, n_int, blocks = 1024, 8, 2, 3
+    total, size = n_int * blocks, n + 1
+    g = H.rng(0xab2)
+    plan = engine.Plan.try_new(n, engine.SOLINAS_P)
+    bnf = M.NttBootstrapKey(plan, dev(H.uniform_u64(g, (small, 1, 2, 2, n)) % np.uint64(engine.SOLINAS_P)), 23, 1, M.BNF)
+    ksk = KS.LweKeyswitchKey(dev(H.uniform_u64(g, (n, 3, small + 1))), 4, 3)
+    key = S.ShortintServerKey(ksk, bnf, 4, 4)
+    row = 8 * size
+    words = H.uniform_u64(g, (3, total + 2 * n_int, size))  # rows [2, 8) are the radix, [0, 2) and [8, 10) beside it
+    prop, add = L().mi_radix_propagate_single_carry_batch, L().mi_radix_add_batch
+    first = n_int * row
+
+    def fresh():
+        return [dev(w) for w in words]
+
+    # carry_out at these byte offsets from the radix's start overlaps it
+    bad = [-row, (total - 1) * row, 0, 2 * row, -first + 8, total * row - 8]
+    for off in bad:
+        a, b, c = fresh()
+        before = [t.clone() for t in (a, b, c)]
+        pa, pb, pc = (t.data_ptr() + first for t in (a, b, c))
+        other_error()
+        answered(prop(key._h, pa, pa + off, blocks, n_int, None), INVALID, "carry_out overlaps")
+        for out, lhs, rhs, carry in [(pa, pb, pc, pa + off), (pa, pb, pc, pb + off), (pa, pb, pc, pc + off),
+                                     (pa, pa, pb, pa + off), (pa, pb, pa, pb + off)]:
+            other_error()
+            answered(add(key._h, out, lhs, rhs, carry, blocks, n_int, None), INVALID, "carry_out overlaps")
+        torch.cuda.synchronize()
+        assert all(torch.equal(t, u) for t, u in zip((a, b, c), before)), off
+    # B = 1: the radix is n_integers rows
+    a = fresh()[0]
+    other_error()
+    answered(prop(key._h, a.data_ptr(), a.data_ptr() + row, 1, 3, None), INVALID, "carry_out overlaps")
+    # accepted: right before and right after the radix, in the same tensor
+    want_r, want_c = dev(words[0][n_int:n_int + total]), torch.zeros((n_int, size), dtype=torch.int64, device="cuda")
+    assert prop(key._h, want_r.data_ptr(), want_c.data_ptr(), blocks, n_int, None) == 0
+    sum_r, sum_c = torch.zeros_like(want_r), torch.zeros_like(want_c)
+    lhs, rhs = dev(words[1][n_int:n_int + total]), dev(words[2][n_int:n_int + total])
+    assert add(key._h, sum_r.data_ptr(), lhs.data_ptr(), rhs.data_ptr(), sum_c.data_ptr(), blocks, n_int, None) == 0
+    for off, rows in [(-first, slice(0, n_int)), (total * row, slice(n_int + total, None))]:
+        a = fresh()[0]
+        pa = a.data_ptr() + first
+        assert prop(key._h, pa, pa + off, blocks, n_int, None) == 0
+        assert torch.equal(a[n_int:n_int + total], want_r) and torch.equal(a[rows], want_c), off
+        assert add(key._h, pa, lhs.data_ptr(), rhs.data_ptr(), pa + off, blocks, n_int, None) == 0
+        assert torch.equal(a[n_int:n_int + total], sum_r) and torch.equal(a[rows], sum_c), off
+    assert prop(key._h, a.data_ptr() + first, None, blocks, n_int, None) == 0  # no carry_out: nothing to overlap
+    torch.cuda.synchronize()

@@ -16,35 +16,8 @@ import tfhe_helpers as H
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = np.uint64(0x5E5E5E5E5E5E5E5E)
-
-
-def oracle_apply(oracle, ks, lwe, luts, lut_index, in_index, mode, drift, ms_params=None):
-    """The expected output rows, and which rows are written at all."""
-    n, small = ks.n, ks.small
-    cur = oracle.lwe_keyswitch(ks.ksk_words, lwe, small, G.KS_BL, G.KS_L)
-    ms = mode
-    if drift:
-        log2n = (2 * n).bit_length() - 1
-        p = MN.Params(*(ms_params or ks.ms_params), log2n)
-        cand, _ = MN.choose_np(cur, ks.zeros_words, p)
-        cur, ms = MN.switch_np(MN.improve_np(cur, ks.zeros_words, cand), log2n), 2
-    n_items = len(lut_index)
-    src = np.arange(n_items) if in_index is None else np.asarray(in_index)
-    live = (src < lwe.shape[0]) & (np.asarray(lut_index) < luts.shape[0])
-    out = np.full((n_items, n + 1), SENTINEL, np.uint64)
-    rows = np.flatnonzero(live)
-    if rows.size:
-        if ms == 2:
-            acc = luts[np.asarray(lut_index)[rows]]
-            rot = ks.ctx.blind_rotate_batch(acc, cur[src[rows]], ks.bsk_ntt, 1, G.PBS_BL, G.PBS_L, bnf=True, ms_mode=2)
-            out[rows] = np.stack([oracle.sample_extract(r, n, 1) for r in rot])
-        else:
-            for l in set(np.asarray(lut_index)[rows].tolist()):
-                sel = rows[np.asarray(lut_index)[rows] == l]
-                out[sel] = ks.ctx.pbs_batch_bnf(cur[src[sel]], luts[l], ks.bsk_ntt, 1, G.PBS_BL, G.PBS_L,
-                                                centered=(ms == 1))
-    return out, live
+SENTINEL = G.SENTINEL
+oracle_apply = G.oracle_apply
 
 
 @pytest.mark.parametrize("which", ["u2048", "u1024"])

@@ -4,6 +4,7 @@
   mi_lwe_linear_combination_batch            test_async_entries[lincomb]          H
   mi_shortint_apply_lut_batch                test_async_entries[apply, apply-fft] H, test_hand_over O
   mi_radix_propagate_single_carry_batch      test_async_entries[propagate]        H, test_hand_over O
+                                             test_async_propagate_on_the_lane_driver  H (N = 8192, forked lanes)
   mi_radix_full_propagate_batch              test_async_entries[full-propagate]   H, test_hand_over O
   mi_radix_add_batch                         test_async_entries[add]              H, test_hand_over O
 
@@ -119,3 +120,18 @@ def test_hand_over(engine, oracle, entry):
             torch.cuda.synchronize()
             for a, b in zip(got[key], outputs):
                 assert torch.equal(a, b), f"stream {key[0]}, round {key[1]} differs from the quiescent run"
+
+
+def test_async_propagate_on_the_lane_driver(engine, oracle):
+    """H for mi_radix_propagate_single_carry_batch where the bootstrap is the multi-pass one: N = 8192 (pbs_large.hip) at
+    m = c = 8, 8 integers of 5 blocks.  Round 1 is 80 items, which the chunk-and-lane driver runs on side streams
+    (pbs_passes.hpp lanes_wanted), the scan rounds 40 items with kept blocks on the caller's stream alone: the
+    composite's scratch and the forked lanes keep the contract together."""
+    ks = G.key_set(engine, oracle, "u8192")
+    I = engine.integer.ServerKey(ks.server("ntt", m=8, c=8))
+    g = H.rng(0x5d20)
+    n_int, blocks = 8, 5
+    radix, carry = G.zeros((n_int, blocks, ks.size)), G.zeros((n_int, ks.size))
+    call = lambda: I._propagate_single_carry(radix, carry)
+    operands = [(radix, *two(lambda: H.uniform_u64(g, (n_int, blocks, ks.size))))]
+    SO.check_case(engine, SO.Case("shortint-propagate-8192", call, operands, [radix, carry], None))

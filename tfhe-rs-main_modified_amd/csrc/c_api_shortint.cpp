@@ -338,10 +338,13 @@ int mi_radix_propagate_single_carry_batch(const mi_shortint_key* key, uint64_t* 
   if (st != MI_OK) return st;
   if (n_blocks > 1 && !single_carry_supported(key->m, key->c)) return single_carry_unsupported();
   if (n_integers == 0) return MI_OK;
+  const size_t B = n_blocks, I = n_integers, T = I * B, big1 = key->big + 1;
+  // carry_out is written after radix: an overlap would destroy blocks
+  if (carry_out && overlap(carry_out, I * big1 * 8, radix, T * big1 * 8))
+    return fail(MI_ERR_INVALID_ARG, "carry_out overlaps radix");
   const hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  const size_t B = n_blocks, I = n_integers, T = I * B, big1 = key->big + 1;
   const uint32_t t32 = (uint32_t)T, b32 = (uint32_t)B;
   // work = msg[T] | st[T]; pack / sum [T]; index arrays: in[2 T], lut[2 T], a[T], b[T], pairs[2 T]; coeff[2 T]
   mi::ScratchBuf buf(3 * T * big1 * sizeof(uint64_t) + 2 * T * sizeof(int64_t) + 8 * T * sizeof(uint32_t), s);
@@ -444,13 +447,16 @@ int mi_radix_add_batch(const mi_shortint_key* key, uint64_t* radix_out, const ui
   if (n_blocks > 1 && !single_carry_supported(key->m, key->c)) return single_carry_unsupported();
   if (n_integers == 0) return MI_OK;
   if (!lhs || !rhs) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  const hipStream_t s = (hipStream_t)stream;
-  DeviceGuard g(key->device);
-  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   const size_t T = n_integers * n_blocks, big1 = key->big + 1, bytes = T * big1 * sizeof(uint64_t);
   for (const uint64_t* p : {lhs, rhs})
     if (p != radix_out && overlap(radix_out, bytes, p, bytes))
       return fail(MI_ERR_INVALID_ARG, "radix_out partially overlaps an operand");
+  for (const uint64_t* p : {(const uint64_t*)radix_out, lhs, rhs})
+    if (carry_out && overlap(carry_out, n_integers * big1 * 8, p, bytes))
+      return fail(MI_ERR_INVALID_ARG, "carry_out overlaps radix_out or an operand");
+  const hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(key->device);
+  if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   {
     mi::ScratchBuf buf(2 * bytes + 4 * T * sizeof(uint32_t), s);
     if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");

@@ -987,7 +987,7 @@ int mi_lwe_linear_combination_batch(uint64_t *lwe_out, const uint64_t *lwe_in, s
  * keyswitch key k N -> n, one bootstrap key of `pbs_engine` (mi_pbs_ntt64_key of the BNF variant, mi_fft64_pbs_key or
  * mi_fft64_multi_bit_pbs_key, passed as const void *) and, optionally, a mi_ms_noise_key (ModulusSwitchConfiguration::
  * DriftTechniqueNoiseReduction); the modulus switch of the bootstrap (MI_MS_STANDARD or MI_MS_CENTERED); and
- * message_modulus / carry_modulus.  It owns the five lookup tables of the radix calls below (uploaded with a blocking
+ * message_modulus / carry_modulus.  It owns the seven lookup tables of the radix calls below (uploaded with a blocking
  * copy at creation).
  * mi_shortint_key_check states the argument rules on plain numbers, the first failing rule answering:
  * MI_ERR_INVALID_ARG "unknown pbs engine"; MI_ERR_UNSUPPORTED for a Solinas-variant NTT key (its input is not a native
@@ -1060,6 +1060,88 @@ int mi_radix_full_propagate_batch(const mi_shortint_key *key, uint64_t *radix, s
                                   void *stream);
 int mi_radix_add_batch(const mi_shortint_key *key, uint64_t *radix_out, const uint64_t *lhs, const uint64_t *rhs,
                        uint64_t *carry_out, size_t n_blocks, size_t n_integers, void *stream);
+
+/* ---- Radix sum of ciphertexts and multiplication (tfhe/src/integer/server_key/radix_parallel) -------------------
+ * unchecked_partial_sum_ciphertexts_vec_parallelized (sum.rs:14-147), unchecked_sum_ciphertexts_vec_parallelized
+ * (sum.rs:155-166), sum_ciphertexts_parallelized (sum.rs:183), compute_terms_for_mul_low (mul.rs:333-400),
+ * unchecked_mul_assign_parallelized (mul.rs:437-460) and mul_parallelized (mul.rs:599-608) on clean operands, batched.
+ * Both calls are fixed sequences of mi_lwe_linear_combination_batch and mi_shortint_apply_lut_batch (written out at
+ * the top of csrc/c_api_radix_mul.cpp) driven by one data-independent schedule; their index arrays are written on
+ * the device from descriptors passed as kernel arguments, so nothing is copied from the host and no call
+ * synchronises.  The two lookup tables of the multiplication, (x, y) -> (x y) mod m and (x y) / m on m x + y, are the
+ * key's sixth and seventh.
+ *
+ * mi_radix_sum_schedule, a host function: the schedule of the sum of n_terms radix terms of n_blocks blocks, term t
+ * being identically zero below block first_block[t] (the blocks the reference skips by degree == 0; NULL: all 0).
+ * s = (m c - 1) / (m - 1) = max_sum_size(Degree(m - 1)) (shortint/server_key/mod.rs) rows of value <= m - 1 fill a
+ * block.  Column b starts as block b of every term with first_block[t] <= b, in term order.  While some column holds
+ * more than s rows, a round runs: every column of at least s rows (exactly s too) gives len / s chunks of its first
+ * rows, in order; each chunk is summed, the sum gives its message (x mod m) and, unless the column is the last, its
+ * carry (x / m); the next list of column b is its last len % s rows, the carries of column b - 1's chunks in chunk
+ * order, the messages of its own chunks in chunk order; columns of fewer than s rows pass through.  At the end block
+ * b is the sum of column b's rows (an empty column: a trivial zero).  *n_rounds gets the round count R; column_len
+ * ((R + 1) x n_blocks, or NULL) the length of every column at the start of round r and, row R, at the end;
+ * column_chunks (R x n_blocks, or NULL) the chunks of every column in round r; rounds_capacity is the R the arrays
+ * have room for (MI_ERR_INVALID_ARG when it is below R; call with NULL arrays first).  MI_ERR_UNSUPPORTED unless m >=
+ * 2 and 2 <= c <= m (with c > m a carry can pass m - 1 and a later chunk m c - 1); MI_ERR_INVALID_ARG for n_blocks =
+ * 0, first_block[t] > n_blocks and n_blocks * n_terms >= 2^22.  n_terms = 0 is valid (no rounds, empty columns). */
+int mi_radix_sum_schedule(size_t n_blocks, size_t n_terms, const uint32_t *first_block, uint64_t message_modulus,
+                          uint64_t carry_modulus, size_t *n_rounds, uint32_t *column_len, uint32_t *column_chunks,
+                          size_t rounds_capacity);
+/* unchecked_sum_ciphertexts_vec_parallelized over a batch: radix_out (n_integers x n_blocks LWEs) = the sum mod
+ * m^n_blocks of n_terms radix batches stored back to back (term t at row t * n_integers * n_blocks of `terms`), every
+ * block clean (< m).  first_block is a host array (read before the call returns) or NULL; rows below first_block[t]
+ * are never read.  The sequence: one linear combination gathers the live rows into the scratch pool; per round of the
+ * schedule one linear combination with terms = s forms every chunk sum of every integer and one
+ * mi_shortint_apply_lut_batch gives every chunk its message and (not in the last column) its carry for one keyswitch;
+ * one linear combination (terms = s, ragged rows padded with 0xFFFFFFFF) forms the block sums into radix_out; then
+ * mi_radix_full_propagate_batch(radix_out).  n_terms = 0 writes trivial zeros (nothing to propagate); n_terms = 1 and 2
+ * go the general way (the reference's shortcut through add_parallelized gives the same values).  radix_out may not
+ * overlap terms (MI_ERR_INVALID_ARG).  Async on `stream`, stream-ordered scratch; the limits of mi_radix_add_batch, and
+ * MI_ERR_INVALID_ARG "batch too large" for n_terms * n_integers * n_blocks >= 2^31; MI_ERR_UNSUPPORTED as the schedule,
+ * and above 128 blocks (the per-column descriptors of a round are one kernel argument).  n_integers = 0 is MI_OK.
+ * Scratch: per integer the rows of the terms plus two rows per chunk of every round; the integers run in passes whose
+ * scratch block stays under 512 MiB (a pass holds at least one integer), each pass the call on its integers, bit for
+ * bit.  mi_radix_sum_pass_integers / mi_radix_mul_pass_integers answer how many integers a pass of such a call holds
+ * (host functions; at most n_integers). */
+int mi_radix_sum_batch(const mi_shortint_key *key, uint64_t *radix_out, const uint64_t *terms, size_t n_terms,
+                       const uint32_t *first_block, size_t n_blocks, size_t n_integers, void *stream);
+int mi_radix_sum_pass_integers(const mi_shortint_key *key, size_t n_terms, const uint32_t *first_block,
+                               size_t n_blocks, size_t n_integers, size_t *pass_integers);
+/* mul_parallelized on clean operands over a batch: radix_out = lhs * rhs mod m^n_blocks.  With B = n_blocks: one
+ * linear combination packs m * lhs[x] + rhs[y] for the B (B + 1) / 2 pairs with x + y < B of every integer (lhs and
+ * rhs staged in one list by two device-to-device copies); one mi_shortint_apply_lut_batch gives every pair its lsb
+ * (x y) mod m and, at m > 2 and x + y < B - 1, its msb (x y) / m, written as the columns of the 2 B - 1 (B at m = 2)
+ * shifted terms of compute_terms_for_mul_low in its chain order, the zero blocks of the shifts never made: the lsb
+ * term of rhs block y starts at block y and holds lsb(lhs[b - y], rhs[y]), the msb term of rhs block y < B - 1 starts
+ * at block y + 1 and holds msb(lhs[b - y - 1], rhs[y]); then the rounds, block sums and propagation of
+ * mi_radix_sum_batch on those columns.  The result equals, bit for bit, the pack, the lookup, a scatter of its
+ * outputs into dense terms and mi_radix_sum_batch with that first_block.  radix_out may be lhs or rhs (it is written
+ * last) and lhs may be rhs; a partial overlap of radix_out with an operand is MI_ERR_INVALID_ARG before any device
+ * call.  MI_ERR_UNSUPPORTED unless 2 <= c = m (the packed operand needs c >= m, the schedule c <= m) and n_blocks <=
+ * 128.  Scratch per integer: the B^2 product rows (B (B + 1) / 2 at m = 2), then the packed pairs and the staged
+ * operands (B (B + 1) / 2 + 2 B rows) or two rows per chunk of every round, whichever is more (1808 rows, 29.6 MB,
+ * per 64-bit integer at m = c = 4, N = 2048: 18 integers per pass), in passes as above. */
+int mi_radix_mul_batch(const mi_shortint_key *key, uint64_t *radix_out, const uint64_t *lhs, const uint64_t *rhs,
+                       size_t n_blocks, size_t n_integers, void *stream);
+int mi_radix_mul_pass_integers(const mi_shortint_key *key, size_t n_blocks, size_t n_integers, size_t *pass_integers);
+/* The index arrays the multiplication driver writes on the device for a pass of n_integers integers, into the
+ * caller's device arrays (for tests, and for a port that issues the stages itself).  Rows are numbered slot-major: slot
+ * v of integer i is row v * n_integers + i of the pool, of the chunk sums and of the packed pairs alike; the pool's
+ * first slots are the products, column by column in the order given with mi_radix_mul_batch (column b at slot b^2, at
+ * b (b + 1) / 2 when m = 2); round r's outputs take the next slots, column by column: the carries of column b - 1's
+ * chunks, then the messages of column b's chunks.  step = 0, the product round: index and coeff (2 entries per packed
+ * row) = the pack's index and coefficient arrays, pair p = d (d + 1) / 2 + y for (x, y), d = x + y, over lhs[I B] |
+ * rhs[I B]; in_index / lut_index (one entry per product row) = the pair's packed row and table 5 (lsb) or 6 (msb).
+ * step = r + 1, round r of the schedule: index (s entries per chunk sum, chunks numbered column by column) = the
+ * pool rows of the chunk; in_index / lut_index (one entry per output row) = the chunk-sum row and table 0 (message)
+ * or 1 (carry).  step = rounds + 1, the block sums: index (s entries per row i * n_blocks + b, padded with
+ * 0xFFFFFFFF); no items.  *n_index / *n_items get the entries written.  `capacity` is the entries each array holds
+ * (coeff too); every step up to `step` is run through the arrays, and MI_ERR_INVALID_ARG answers before any launch
+ * when one needs more.  Async on `stream`. */
+int mi_radix_mul_index_arrays(uint64_t message_modulus, uint64_t carry_modulus, size_t n_blocks, size_t n_integers,
+                              size_t step, uint32_t *index, int64_t *coeff, uint32_t *in_index, uint32_t *lut_index,
+                              size_t capacity, size_t *n_index, size_t *n_items, int device, void *stream);
 
 #ifdef __cplusplus
 }

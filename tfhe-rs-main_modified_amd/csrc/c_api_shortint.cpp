@@ -47,35 +47,14 @@
 #include "c_api_internal.hpp"
 #include "lwe_linear_algebra_launch.hpp"
 #include "scratch.hpp"
+#include "shortint_internal.hpp"
 
 using namespace mi::capi;
-
-enum { LUT_MSG = 0, LUT_CARRY = 1, LUT_STATE0 = 2, LUT_STATE = 3, LUT_SCAN = 4, N_KEY_LUTS = 5 };
-
-struct mi_shortint_key {
-  const mi_lwe_ksk* ksk = nullptr;
-  int engine = 0;
-  const void* pbs = nullptr;
-  const mi_ms_noise_key* ms_noise = nullptr;
-  int ms_mode = 0;
-  uint64_t m = 0, c = 0;
-  size_t big = 0, small_ = 0, n = 0;  // k N, the small LWE dimension, N
-  int k = 1, device = 0;
-  uint64_t* d_luts = nullptr;  // N_KEY_LUTS GLWEs of the radix drivers
-};
+using namespace mi::shortint;
 
 namespace {
 
-constexpr size_t MAX_ITEMS = 0x3FFFFFull;
-
-int hip_status(hipError_t e, const char* what) { return e == hipSuccess ? MI_OK : hip_fail(e, what); }
-
 bool pow2(uint64_t v) { return v != 0 && (v & (v - 1)) == 0; }
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
 
 // block values up to 2 (m - 1) and the packed scan operand 2 m + 2 must stay below m c
 bool single_carry_supported(uint64_t m, uint64_t c) { return m * c >= 16 && c <= m && 2 * m + 2 < m * c; }
@@ -99,15 +78,6 @@ int pbs_call(const mi_shortint_key* key, uint64_t* out, const uint64_t* in, cons
       return mi_fft64_multi_bit_pbs_batch_lut_indexed((const mi_fft64_multi_bit_pbs_key*)key->pbs, out, in, luts, idx,
                                                       n_lut, items, stream);
   }
-}
-
-int check_radix(const mi_shortint_key* key, const void* radix, size_t n_blocks, size_t n_integers) {
-  if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
-  if (n_blocks == 0) return fail(MI_ERR_INVALID_ARG, "n_blocks is 0");
-  if (n_blocks > MAX_ITEMS || (n_integers && n_blocks > MAX_ITEMS / 2 / n_integers))
-    return fail(MI_ERR_INVALID_ARG, "batch too large");
-  if (n_integers && !radix) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  return MI_OK;
 }
 
 // out[j] = in[j] + in[T + j - 1] for block b >= 1, in[j] for block 0, over in = msg[T] | carry-like[T]
@@ -236,7 +206,9 @@ int mi_shortint_key_create(const mi_lwe_ksk* ksk, int pbs_engine, const void* pb
                  : l == LUT_CARRY  ? x / m
                  : l == LUT_STATE0 ? (uint64_t)(x >= m)
                  : l == LUT_STATE  ? (x >= m ? 1 : x == m - 1 ? 2 : 0)
-                                   : (cur == 2 ? prev : cur);
+                 : l == LUT_SCAN   ? (cur == 2 ? prev : cur)
+                 : l == LUT_MUL_LSB ? (cur * prev) % m
+                                    : (cur * prev) / m;
     }
     st = mi_shortint_lut_fill(luts.data() + l * per, n, k, message_modulus, carry_modulus, table.data(), sup);
     if (st != MI_OK) return st;

@@ -223,6 +223,13 @@ _SIGS = {
     "mi_radix_propagate_single_carry_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
     "mi_radix_full_propagate_batch": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "mi_radix_add_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "mi_radix_sum_schedule": (_int, [_sz, _sz, _vp, _u64, _u64, ctypes.POINTER(_sz), _vp, _vp, _sz]),
+    "mi_radix_sum_batch": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "mi_radix_sum_pass_integers": (_int, [_vp, _sz, _vp, _sz, _sz, ctypes.POINTER(_sz)]),
+    "mi_radix_mul_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "mi_radix_mul_pass_integers": (_int, [_vp, _sz, _sz, ctypes.POINTER(_sz)]),
+    "mi_radix_mul_index_arrays": (_int, [_u64, _u64, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz),
+                                         ctypes.POINTER(_sz), _int, _vp]),
 }
 
 

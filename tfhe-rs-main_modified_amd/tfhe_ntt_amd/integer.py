@@ -8,6 +8,8 @@ Reference (paths relative to tfhe/src/integer/server_key):
 * ``full_propagate_parallelized``                radix_parallel/mod.rs:228 (partial_propagate :91-201)
 * ``propagate_single_carry_parallelized``        radix_parallel/add.rs (compute_prefix_sum_hillis_steele :1452-1487)
 * ``bitand_parallelized`` / ``bitor_parallelized`` / ``bitxor_parallelized``   radix_parallel/bitwise_op.rs
+* ``unchecked_sum_ciphertexts_vec_parallelized`` / ``sum_ciphertexts_parallelized``   radix_parallel/sum.rs:155-166, :183
+* ``mul_parallelized``                           radix_parallel/mul.rs:599-608 (compute_terms_for_mul_low :333-400)
 
 A ``RadixCiphertext`` is a batch of unsigned integers: a device tensor (n_integers, n_blocks, k N + 1) of shortint
 blocks, least significant first, and one degree per block position on the host (the largest value a block at that
@@ -116,6 +118,49 @@ class ServerKey:
         out = self.key.unchecked_scalar_add(ct.blocks, pts)
         self._propagate_single_carry(out)
         return RadixCiphertext(out, [m - 1] * n_blocks)
+
+    def unchecked_sum_ciphertexts_vec_parallelized(self, ciphertexts, first_block=None):
+        """The sum mod m^B of a list of clean ``RadixCiphertext`` of one shape (``mi_radix_sum_batch``); ``None`` for an
+        empty list, as the reference.  ``first_block[t]``: term t is identically zero below that block (the blocks the
+        reference skips by ``degree == 0``) and its rows there are not read."""
+        import ctypes
+
+        import torch
+
+        ciphertexts = list(ciphertexts)
+        if not ciphertexts:
+            return None
+        for ct in ciphertexts:
+            self._same_shape(ciphertexts[0], ct)
+            if not self._clean(ct):
+                raise ValueError("sum_ciphertexts_parallelized takes clean operands here: call "
+                                 "full_propagate_parallelized first")
+        if first_block is not None and len(first_block) != len(ciphertexts):
+            raise ValueError(f"assertion failed: {len(first_block)} first blocks for {len(ciphertexts)} terms")
+        first = ciphertexts[0]
+        terms = torch.stack([ct.blocks for ct in ciphertexts]).contiguous()
+        out = torch.empty_like(first.blocks)
+        fb = (ctypes.c_uint32 * len(ciphertexts))(*[int(f) for f in first_block]) if first_block is not None else None
+        check(lib().mi_radix_sum_batch(self.key._h, _dev(out, "out"), _dev(terms, "terms"), len(ciphertexts), fb,
+                                       first.n_blocks, first.n_integers, _stream(out)))
+        return RadixCiphertext(out, [self.key.message_modulus - 1] * first.n_blocks)
+
+    def sum_ciphertexts_parallelized(self, ciphertexts):
+        """``sum_ciphertexts_parallelized`` (radix_parallel/sum.rs:183) on clean operands."""
+        return self.unchecked_sum_ciphertexts_vec_parallelized(ciphertexts)
+
+    def mul_parallelized(self, lhs: RadixCiphertext, rhs: RadixCiphertext) -> RadixCiphertext:
+        """lhs * rhs mod m^B for clean operands (``mi_radix_mul_batch``; radix_parallel/mul.rs:599-608)."""
+        import torch
+
+        self._same_shape(lhs, rhs)
+        for ct in (lhs, rhs):
+            if not self._clean(ct):
+                raise ValueError("mul_parallelized takes clean operands here: call full_propagate_parallelized first")
+        out = torch.empty_like(lhs.blocks)
+        check(lib().mi_radix_mul_batch(self.key._h, _dev(out, "out"), _dev(lhs.blocks, "lhs"), _dev(rhs.blocks, "rhs"),
+                                       lhs.n_blocks, lhs.n_integers, _stream(out)))
+        return RadixCiphertext(out, [self.key.message_modulus - 1] * lhs.n_blocks)
 
     def _bitwise(self, lhs, rhs, name, f):
         self._same_shape(lhs, rhs)

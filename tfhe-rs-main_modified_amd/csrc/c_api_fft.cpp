@@ -120,7 +120,15 @@ int make_plan(size_t n, int device, mi_fft64_plan** out) {
 
 constexpr int MAX_GENERIC_K = 16;
 
-int check_shape(const mi_fft64_plan* plan, int k, int base_log, int level) {
+hipError_t reorder_any(const mi_fft64_plan* plan, double* out, const double* in, size_t polys, bool to_std,
+                       hipStream_t s) {
+  return plan->generic ? mi::launch_fftg_reorder(out, in, polys, to_std, plan->gtables, s)
+                       : mi::launch_fft64_reorder(out, in, polys, to_std, s);
+}
+
+}  // namespace
+
+int mi::capi::check_fft64_shape(const mi_fft64_plan* plan, int k, int base_log, int level) {
   if (!plan) return fail(MI_ERR_INVALID_ARG, "plan is NULL");
   if (level < 1 || base_log < 1 || base_log * level > 63)
     return fail(MI_ERR_INVALID_ARG, "decomposition must satisfy level >= 1, base_log >= 1, base_log*level < 64");
@@ -129,14 +137,6 @@ int check_shape(const mi_fft64_plan* plan, int k, int base_log, int level) {
                                     "at other N");
   return MI_OK;
 }
-
-hipError_t reorder_any(const mi_fft64_plan* plan, double* out, const double* in, size_t polys, bool to_std,
-                       hipStream_t s) {
-  return plan->generic ? mi::launch_fftg_reorder(out, in, polys, to_std, plan->gtables, s)
-                       : mi::launch_fft64_reorder(out, in, polys, to_std, s);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -251,7 +251,7 @@ int mi_bsk_to_fourier64(const mi_fft64_plan* plan, const uint64_t* bsk_std, doub
 
 int mi_fft64_ext_product_batch(const mi_fft64_plan* plan, uint64_t* out_glwe, const uint64_t* in_glwe,
                                const double* ggsw_fourier, int k, int base_log, int level, size_t batch, void* stream) {
-  int st = check_shape(plan, k, base_log, level);
+  int st = check_fft64_shape(plan, k, base_log, level);
   if (st != MI_OK) return st;
   if (batch == 0) return MI_OK;
   if (!out_glwe || !in_glwe || !ggsw_fourier) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
@@ -267,7 +267,7 @@ int mi_fft64_ext_product_batch(const mi_fft64_plan* plan, uint64_t* out_glwe, co
 
 int mi_fft64_cmux_batch(const mi_fft64_plan* plan, uint64_t* ct0, uint64_t* ct1, const double* ggsw_fourier, int k,
                         int base_log, int level, size_t batch, void* stream) {
-  int st = check_shape(plan, k, base_log, level);
+  int st = check_fft64_shape(plan, k, base_log, level);
   if (st != MI_OK) return st;
   if (batch == 0) return MI_OK;
   if (!ct0 || !ct1 || !ggsw_fourier) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
@@ -285,7 +285,7 @@ int mi_fft64_cmux_batch(const mi_fft64_plan* plan, uint64_t* ct0, uint64_t* ct1,
 static int ext_indexed(bool cmux, const mi_fft64_plan* plan, uint64_t* out, uint64_t* in, const double* ggsw_list,
                        const uint32_t* ggsw_index, size_t n_ggsw, int k, int base_log, int level, size_t batch,
                        void* stream) {
-  int st = check_shape(plan, k, base_log, level);
+  int st = check_fft64_shape(plan, k, base_log, level);
   if (st != MI_OK) return st;
   if (batch == 0) return MI_OK;
   if (!out || !in || !ggsw_list || !ggsw_index) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
@@ -317,7 +317,7 @@ int mi_fft64_pbs_key_create(const mi_fft64_plan* plan, const double* fbsk, size_
                             int level, mi_fft64_pbs_key** out_key) {
   if (!out_key) return fail(MI_ERR_INVALID_ARG, "out_key is NULL");
   *out_key = nullptr;
-  int st = check_shape(plan, k, base_log, level);
+  int st = check_fft64_shape(plan, k, base_log, level);
   if (st != MI_OK) return st;
   if (n_lwe == 0 || n_lwe > 0xFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "n_lwe out of range");
   if (!fbsk) return fail(MI_ERR_INVALID_ARG, "bsk is NULL");
@@ -442,7 +442,7 @@ int mi_fft64_pbs_key_load(const mi_fft64_plan* plan, const uint8_t* bytes, size_
   if (glwe < 2 || glwe > MAX_GENERIC_K + 1 || level < 1 || level > 63 || base_log < 1 || base_log > 63 ||
       !fourier_layout(m, n_lwe, glwe, level, base_log, ver, &L) || L.chunks != chunks)
     return fail(MI_ERR_INVALID_ARG, "Fourier BSK: the polynomial count does not match n_lwe x level x glwe_size^2");
-  int st = check_shape(plan, (int)glwe - 1, (int)base_log, (int)level);
+  int st = check_fft64_shape(plan, (int)glwe - 1, (int)base_log, (int)level);
   if (st != MI_OK) return st;
   if (n_lwe == 0 || n_lwe > 0xFFFFFFFull) return fail(MI_ERR_INVALID_ARG, "Fourier BSK: n_lwe out of range");
   for (uint64_t c = 0; c < chunks; ++c)

@@ -104,6 +104,23 @@ inline int fail(int status, const std::string& msg) {
 inline int hip_fail(hipError_t e, const char* what) {
   return fail(MI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+inline int hip_status(hipError_t e, const char* what) { return e == hipSuccess ? MI_OK : hip_fail(e, what); }
+
+// The early returns of a driver (its scratch is RAII): of a status that is not MI_OK, and of a failed hipError_t
+#define MI_TRY(call) \
+  do { const int mi_try_ = (call); if (mi_try_ != MI_OK) return mi_try_; } while (0)
+#define MI_TRY_HIP(launch, what) MI_TRY(::mi::capi::hip_status((launch), (what)))
+// `const W w`: a workspace of carve.hpp on a scratch block of its size, for the scope; returns MI_ERR_OOM without one
+#define MI_CARVED_SCRATCH(W, w, stream, ...)                                            \
+  mi::ScratchBuf w##_buf(mi::carved_bytes<W>(__VA_ARGS__), stream);                     \
+  if (!w##_buf.ok()) return ::mi::capi::fail(MI_ERR_OOM, "scratch allocation failed"); \
+  const W w = mi::carve_on<W>(w##_buf.ptr(), __VA_ARGS__)
+
+// whether two byte ranges share a byte; an empty range overlaps nothing
+inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
 
 struct DeviceGuard {
   int prev = -1;
@@ -137,6 +154,9 @@ bool pbs_key_needs_copy(const mi_ntt64_plan* plan, int variant, int k, int base_
 // `stream`
 int prepare_pbs_key(const mi_ntt64_plan* plan, int variant, int k, int base_log, int level, u64* dst, const u64* src,
                     size_t count, hipStream_t stream);
+
+// c_api_fft.cpp, shared with c_api_wopbs.cpp: the shape rules of the f64-FFT external product, CMUX and PBS
+int check_fft64_shape(const mi_fft64_plan* plan, int k, int base_log, int level);
 
 }  // namespace capi
 }  // namespace mi

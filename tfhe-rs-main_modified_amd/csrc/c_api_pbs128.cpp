@@ -104,8 +104,7 @@ int ext_common(const mi_pbs128_key* key, bool cmux, size_t ggsw_index, uint64_t*
   // the recombination writes `out` after `in` was read by another pass: overlapping operands would not give the
   // reference's result
   const uintptr_t bytes = (uintptr_t)batch * ((size_t)key->shape.k + 1) * key->plan->n * 16;
-  if ((uintptr_t)out < (uintptr_t)in + bytes && (uintptr_t)in < (uintptr_t)out + bytes)
-    return fail(MI_ERR_INVALID_ARG, "buffers overlap");
+  if (overlap(out, bytes, in, bytes)) return fail(MI_ERR_INVALID_ARG, "buffers overlap");
   DeviceGuard g(key->plan->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   const hipError_t e = mi::launch_ext_product128(cmux, out, in, key->prepared + ggsw_index * mi::pbs128_ggsw_words(key->shape),
@@ -131,10 +130,6 @@ int rotate_common(const mi_pbs128_key* key, uint64_t* lwe_out, uint64_t* acc_glw
                                  ms_mode == MI_MS_CENTERED, ms_mode == MI_MS_PRE_SWITCHED, key->shape,
                                  route_of(key->plan), (hipStream_t)stream);
   return e == hipSuccess ? MI_OK : hip_fail(e, lut ? "pbs launch" : "blind rotation launch");
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  return (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
 }
 
 // the multi-bit blind rotation behind mi_pbs128_multi_bit_blind_rotate_batch (lut NULL, in place) and

@@ -66,10 +66,11 @@ struct Round {
 struct Schedule {
   uint32_t n_cols = 0, s = 0;
   uint32_t n_initial = 0, n_slots = 0;  // slots of the initial columns, of the whole pool
-  std::vector<uint32_t> len0;
   std::vector<Round> rounds;
   std::vector<mi::SumColumn> last;  // list_off and len of the columns after the rounds
   uint32_t max_chunks = 0, max_items = 0;
+  mi::PassLayout lay;   // of a pass, and the integers of one (plan_passes)
+  size_t per_pass = 0;
 };
 
 int schedule_rules(uint64_t m, uint64_t c) {
@@ -83,7 +84,7 @@ int schedule_rules(uint64_t m, uint64_t c) {
 // the rounds of sum.rs:75-126 on column lengths
 int build_schedule(const std::vector<uint32_t>& len0, uint64_t m, uint64_t c, Schedule& out) {
   const uint32_t B = (uint32_t)len0.size(), s = (uint32_t)((m * c - 1) / (m - 1));
-  out.n_cols = B, out.s = s, out.len0 = len0;
+  out.n_cols = B, out.s = s;
   std::vector<mi::SumColumn> cur(B);
   uint32_t off = 0;
   for (uint32_t b = 0; b < B; ++b) {
@@ -140,97 +141,56 @@ std::vector<uint32_t> mul_lengths(size_t n_blocks, uint64_t m) {
   return len0;
 }
 
-struct PassLayout {
-  size_t rows = 0;         // of the pool and what follows it, per integer
-  size_t tail_rows = 0;    // rows after the initial columns
-  size_t sum_idx = 0, item_idx = 0, list_len = 0, pack_idx = 0, gather_idx = 0;  // u32 / pair entries per integer
-  size_t bytes = 0;        // per integer (the lists, which the integers share, counted once more)
-};
-
-PassLayout pass_layout(const Schedule& sc, size_t big1, bool mul) {
-  PassLayout p;
-  const size_t B = sc.n_cols, pairs = mul ? B * (B + 1) / 2 : 0;
-  p.tail_rows = std::max<size_t>((sc.n_slots - sc.n_initial) + sc.max_chunks, mul ? pairs + 2 * B : 0);
-  p.rows = sc.n_initial + p.tail_rows;
-  p.sum_idx = std::max<size_t>(sc.max_chunks, B) * sc.s;
-  p.item_idx = std::max<size_t>(sc.max_items, mul ? sc.n_initial : 0);
-  p.list_len = sc.n_initial;
-  p.pack_idx = 2 * pairs;
-  p.gather_idx = mul ? 0 : sc.n_initial;
-  p.bytes = p.rows * big1 * sizeof(uint64_t) + p.pack_idx * sizeof(int64_t) +
-            (p.sum_idx + 2 * p.item_idx + p.pack_idx + p.gather_idx + 2 * p.list_len) * sizeof(uint32_t);
-  return p;
-}
-
-int integers_per_pass(const Schedule& sc, const PassLayout& p, size_t n_integers, size_t* out) {
-  const size_t widest = std::max<size_t>({p.rows, p.sum_idx, p.item_idx, p.pack_idx, 1});
+// after an entry point's own checks: the schedule, the layout of a pass (carve.hpp) and the integers one pass takes
+int plan_passes(uint64_t m, uint64_t c, size_t big1, const std::vector<uint32_t>& len0, bool mul, size_t n_integers,
+                Schedule& sc) {
+  MI_TRY(build_schedule(len0, m, c, sc));
+  const mi::PassLayout& p = sc.lay = mi::pass_layout(sc.n_initial, sc.n_slots, sc.max_chunks, sc.max_items, sc.s,
+                                                     sc.n_cols, big1, mul);
+  const size_t widest = std::max<size_t>({p.list_len + p.tail_rows, p.sum_idx, p.item_idx, p.pack_idx, 1});
   if (widest > MAX_ITEMS) return fail(MI_ERR_INVALID_ARG, "batch too large");
-  size_t n = std::max<size_t>(RADIX_SUM_CAP_BYTES / p.bytes, 1);
-  n = std::min(n, MAX_ITEMS / widest);
-  *out = std::min(n, std::max<size_t>(n_integers, 1));
+  const size_t n = std::min(std::max<size_t>(RADIX_SUM_CAP_BYTES / p.bytes, 1), MAX_ITEMS / widest);
+  sc.per_pass = std::min(n, std::max<size_t>(n_integers, 1));
   return MI_OK;
 }
 
-struct Workspace {
-  uint64_t *pool, *tail;
-  int64_t* pack_coeff;
-  uint32_t *sum_idx, *in_idx, *lut_idx, *pack_idx, *gather_idx, *list[2];
-};
-
-Workspace carve(void* base, const PassLayout& p, const Schedule& sc, size_t big1, size_t I) {
-  Workspace w;
-  w.pool = (uint64_t*)base;
-  w.tail = w.pool + sc.n_initial * I * big1;
-  w.pack_coeff = (int64_t*)(w.pool + p.rows * I * big1);
-  w.sum_idx = (uint32_t*)(w.pack_coeff + p.pack_idx * I);
-  w.in_idx = w.sum_idx + p.sum_idx * I;
-  w.lut_idx = w.in_idx + p.item_idx * I;
-  w.pack_idx = w.lut_idx + p.item_idx * I;
-  w.gather_idx = w.pack_idx + p.pack_idx * I;
-  w.list[0] = w.gather_idx + p.gather_idx * I;
-  w.list[1] = w.list[0] + p.list_len;
-  return w;
-}
-
-mi::SumRound descriptor(const Schedule& sc, const std::vector<mi::SumColumn>& col, size_t I) {
+// the descriptor of round r of a schedule, or of the block sums at r = the round count
+mi::SumRound round_descriptor(const Schedule& sc, size_t r, size_t I) {
+  const bool last = r == sc.rounds.size();
+  const std::vector<mi::SumColumn>& col = last ? sc.last : sc.rounds[r].col;
   mi::SumRound d = {};
-  d.n_cols = sc.n_cols, d.s = sc.s, d.integers = (uint32_t)I;
+  d.n_cols = sc.n_cols, d.s = sc.s, d.integers = (uint32_t)I, d.final_round = last;
   std::copy(col.begin(), col.end(), d.col);
+  if (!last) d.n_chunks = sc.rounds[r].n_chunks, d.n_items = sc.rounds[r].n_items;
+  if (!last) d.new_total = sc.rounds[r].new_total, d.out_base = sc.rounds[r].out_base;
   return d;
 }
 
-// steps 2 to 4 of the sum on a pool whose initial columns are filled: the rounds, the block sums, the propagation
-int run_rounds(const mi_shortint_key* key, uint64_t* radix_out, const Schedule& sc, const Workspace& w, size_t I,
-               void* stream) {
-  const hipStream_t s = (hipStream_t)stream;
-  const size_t big1 = key->big + 1;
-  uint64_t* sums = w.pool + (size_t)sc.n_slots * I * big1;
+// The first n rounds of a schedule (the round count + 1: the block sums too).  Each writes its index arrays: a round
+// sum_idx, in_idx, lut_idx and its next list from the list before, the block sums sum_idx alone.  With a key (steps 2
+// to 4 of the sum, on a filled pool) each launch is followed by its LC and APPLY, the last by the propagation.
+int run_rounds(const mi_shortint_key* key, uint64_t* radix_out, const Schedule& sc, const mi::PassWork& w, size_t n,
+               size_t I, void* stream) {
   const uint32_t* prev = nullptr;  // round 0: the pool is column-major, a list entry is its own slot
-  int st = MI_OK, flip = 0;
-  for (const Round& r : sc.rounds) {
-    mi::SumRound d = descriptor(sc, r.col, I);
-    d.n_chunks = r.n_chunks, d.n_items = r.n_items, d.new_total = r.new_total, d.out_base = r.out_base;
-    uint32_t* next = w.list[flip];
-    st = hip_status(mi::launch_radix_sum_round(w.sum_idx, w.in_idx, w.lut_idx, next, prev, d, LUT_MSG, LUT_CARRY, s),
-                    "radix sum index launch");
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(sums, w.pool, key->big, (size_t)r.out_base * I, (size_t)r.n_chunks * I, sc.s,
-                                           w.sum_idx, nullptr, nullptr, key->device, stream);
-    if (st == MI_OK)
-      st = mi_shortint_apply_lut_batch(key, w.pool + (size_t)r.out_base * I * big1, sums, (size_t)r.n_chunks * I,
-                                       w.in_idx, key->d_luts, w.lut_idx, N_KEY_LUTS, (size_t)r.n_items * I, stream);
-    if (st != MI_OK) return st;
-    prev = next, flip ^= 1;
+  for (size_t r = 0; r < n; ++r) {
+    const bool last = r == sc.rounds.size();
+    const mi::SumRound d = round_descriptor(sc, r, I);
+    uint32_t* next = last ? nullptr : w.list[r & 1];
+    MI_TRY_HIP(mi::launch_radix_sum_round(w.sum_idx, last ? nullptr : w.in_idx, last ? nullptr : w.lut_idx, next, prev,
+                                          d, LUT_MSG, LUT_CARRY, (hipStream_t)stream),
+               "radix sum index launch");
+    prev = next;
+    if (!key) continue;
+    const size_t big1 = key->big + 1, slots = last ? sc.n_slots : d.out_base;
+    const size_t n_sums = last ? I * sc.n_cols : (size_t)d.n_chunks * I;
+    uint64_t* sums = last ? radix_out : w.pool + (size_t)sc.n_slots * I * big1;
+    MI_TRY(mi_lwe_linear_combination_batch(sums, w.pool, key->big, slots * I, n_sums, sc.s, w.sum_idx, nullptr, nullptr,
+                                           key->device, stream));
+    if (!last)
+      MI_TRY(mi_shortint_apply_lut_batch(key, w.pool + slots * I * big1, sums, n_sums, w.in_idx, key->d_luts, w.lut_idx,
+                                         N_KEY_LUTS, (size_t)d.n_items * I, stream));
   }
-  mi::SumRound d = descriptor(sc, sc.last, I);
-  d.final_round = 1;
-  st = hip_status(mi::launch_radix_sum_round(w.sum_idx, nullptr, nullptr, nullptr, prev, d, LUT_MSG, LUT_CARRY, s),
-                  "radix sum index launch");
-  if (st == MI_OK)
-    st = mi_lwe_linear_combination_batch(radix_out, w.pool, key->big, (size_t)sc.n_slots * I, I * sc.n_cols, sc.s,
-                                         w.sum_idx, nullptr, nullptr, key->device, stream);
-  if (st == MI_OK) st = mi_radix_full_propagate_batch(key, radix_out, sc.n_cols, I, stream);
-  return st;
+  return key ? mi_radix_full_propagate_batch(key, radix_out, sc.n_cols, I, stream) : MI_OK;  // 4.
 }
 
 int too_many_blocks() {
@@ -244,12 +204,11 @@ extern "C" {
 int mi_radix_sum_schedule(size_t n_blocks, size_t n_terms, const uint32_t* first_block, uint64_t message_modulus,
                           uint64_t carry_modulus, size_t* n_rounds, uint32_t* column_len, uint32_t* column_chunks,
                           size_t rounds_capacity) {
-  int st = schedule_rules(message_modulus, carry_modulus);
-  if (st != MI_OK) return st;
+  MI_TRY(schedule_rules(message_modulus, carry_modulus));
   std::vector<uint32_t> len0;
-  if ((st = initial_lengths(n_blocks, n_terms, first_block, len0)) != MI_OK) return st;
+  MI_TRY(initial_lengths(n_blocks, n_terms, first_block, len0));
   Schedule sc;
-  if ((st = build_schedule(len0, message_modulus, carry_modulus, sc)) != MI_OK) return st;
+  MI_TRY(build_schedule(len0, message_modulus, carry_modulus, sc));
   if (n_rounds) *n_rounds = sc.rounds.size();
   if (!column_len && !column_chunks) return MI_OK;
   if (rounds_capacity < sc.rounds.size()) return fail(MI_ERR_INVALID_ARG, "rounds_capacity is below the round count");
@@ -268,35 +227,34 @@ int mi_radix_sum_pass_integers(const mi_shortint_key* key, size_t n_terms, const
                                size_t n_integers, size_t* pass_integers) {
   if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
   if (!pass_integers) return fail(MI_ERR_INVALID_ARG, "pass_integers is NULL");
-  int st = schedule_rules(key->m, key->c);
-  if (st != MI_OK) return st;
+  MI_TRY(schedule_rules(key->m, key->c));
   std::vector<uint32_t> len0;
-  if ((st = initial_lengths(n_blocks, n_terms, first_block, len0)) != MI_OK) return st;
+  MI_TRY(initial_lengths(n_blocks, n_terms, first_block, len0));
   if (n_blocks > mi::RADIX_MAX_BLOCKS) return too_many_blocks();
   Schedule sc;
-  if ((st = build_schedule(len0, key->m, key->c, sc)) != MI_OK) return st;
-  return integers_per_pass(sc, pass_layout(sc, key->big + 1, false), n_integers, pass_integers);
+  MI_TRY(plan_passes(key->m, key->c, key->big + 1, len0, false, n_integers, sc));
+  *pass_integers = sc.per_pass;
+  return MI_OK;
 }
 
 int mi_radix_mul_pass_integers(const mi_shortint_key* key, size_t n_blocks, size_t n_integers, size_t* pass_integers) {
   if (!key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
   if (!pass_integers) return fail(MI_ERR_INVALID_ARG, "pass_integers is NULL");
   if (n_blocks == 0) return fail(MI_ERR_INVALID_ARG, "n_blocks is 0");
-  int st = schedule_rules(key->m, key->c);
-  if (st != MI_OK) return st;
+  MI_TRY(schedule_rules(key->m, key->c));
   if (n_blocks > mi::RADIX_MAX_BLOCKS) return too_many_blocks();
   Schedule sc;
-  if ((st = build_schedule(mul_lengths(n_blocks, key->m), key->m, key->c, sc)) != MI_OK) return st;
-  return integers_per_pass(sc, pass_layout(sc, key->big + 1, true), n_integers, pass_integers);
+  MI_TRY(plan_passes(key->m, key->c, key->big + 1, mul_lengths(n_blocks, key->m), true, n_integers, sc));
+  *pass_integers = sc.per_pass;
+  return MI_OK;
 }
 
 int mi_radix_sum_batch(const mi_shortint_key* key, uint64_t* radix_out, const uint64_t* terms, size_t n_terms,
                        const uint32_t* first_block, size_t n_blocks, size_t n_integers, void* stream) {
-  int st = check_radix(key, radix_out, n_blocks, n_integers);
-  if (st != MI_OK) return st;
-  if ((st = schedule_rules(key->m, key->c)) != MI_OK) return st;
+  MI_TRY(check_radix(key, radix_out, n_blocks, n_integers));
+  MI_TRY(schedule_rules(key->m, key->c));
   std::vector<uint32_t> len0;
-  if ((st = initial_lengths(n_blocks, n_terms, first_block, len0)) != MI_OK) return st;
+  MI_TRY(initial_lengths(n_blocks, n_terms, first_block, len0));
   if (n_blocks > mi::RADIX_MAX_BLOCKS) return too_many_blocks();
   const size_t B = n_blocks, NI = n_integers, big1 = key->big + 1, T = NI * B;
   if (n_terms && T > 0x7FFFFFFFull / n_terms) return fail(MI_ERR_INVALID_ARG, "batch too large");
@@ -305,24 +263,21 @@ int mi_radix_sum_batch(const mi_shortint_key* key, uint64_t* radix_out, const ui
   if (overlap(radix_out, T * big1 * 8, terms, n_terms * T * big1 * 8))
     return fail(MI_ERR_INVALID_ARG, "radix_out overlaps terms");
   Schedule sc;
-  if ((st = build_schedule(len0, key->m, key->c, sc)) != MI_OK) return st;
-  const PassLayout lay = pass_layout(sc, big1, false);
-  size_t per_pass = 0;
-  if ((st = integers_per_pass(sc, lay, NI, &per_pass)) != MI_OK) return st;
+  MI_TRY(plan_passes(key->m, key->c, big1, len0, false, NI, sc));
   const hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   if (n_terms == 0)  // None in the reference: the caller's trivial zero, which has nothing to propagate
     return mi_lwe_linear_combination_batch(radix_out, nullptr, key->big, 0, T, 0, nullptr, nullptr, nullptr, key->device,
                                            stream);
-  mi::ScratchBuf buf(lay.bytes * per_pass, s);
+  mi::ScratchBuf buf(sc.lay.bytes * sc.per_pass, s);
   if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-  for (size_t i0 = 0; i0 < NI && st == MI_OK; i0 += per_pass) {
-    const size_t I = std::min(per_pass, NI - i0);
-    const Workspace w = carve(buf.ptr(), lay, sc, big1, I);
-    // the gather: the live rows of the terms into the column-major pool
+  for (size_t i0 = 0; i0 < NI; i0 += sc.per_pass) {
+    const size_t I = std::min(sc.per_pass, NI - i0);
+    const mi::PassWork w = mi::carve_on<mi::PassWork>(buf.ptr(), sc.lay, big1, I);
+    // 1. the gather: the live rows of the terms into the column-major pool
     std::vector<uint32_t> rank(B, 0);
-    for (size_t t0 = 0; t0 < n_terms && st == MI_OK; t0 += mi::RADIX_GATHER_TERMS) {
+    for (size_t t0 = 0; t0 < n_terms; t0 += mi::RADIX_GATHER_TERMS) {
       mi::SumGather ga = {};
       ga.n_cols = (uint32_t)B, ga.n_terms = (uint32_t)std::min<size_t>(mi::RADIX_GATHER_TERMS, n_terms - t0);
       ga.t0 = (uint32_t)t0, ga.integers = (uint32_t)I, ga.n_integers = (uint32_t)NI, ga.i0 = (uint32_t)i0;
@@ -331,21 +286,19 @@ int mi_radix_sum_batch(const mi_shortint_key* key, uint64_t* radix_out, const ui
         ga.first[u] = first_block ? first_block[t0 + u] : 0;
         for (size_t b = ga.first[u]; b < B; ++b) ++rank[b];
       }
-      st = hip_status(mi::launch_radix_sum_gather(w.gather_idx, ga, s), "radix sum index launch");
+      MI_TRY_HIP(mi::launch_radix_sum_gather(w.gather_idx, ga, s), "radix sum index launch");
     }
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(w.pool, terms, key->big, n_terms * T, (size_t)sc.n_initial * I, 1,
-                                           w.gather_idx, nullptr, nullptr, key->device, stream);
-    if (st == MI_OK) st = run_rounds(key, radix_out + i0 * B * big1, sc, w, I, stream);
+    MI_TRY(mi_lwe_linear_combination_batch(w.pool, terms, key->big, n_terms * T, (size_t)sc.n_initial * I, 1,
+                                           w.gather_idx, nullptr, nullptr, key->device, stream));
+    MI_TRY(run_rounds(key, radix_out + i0 * B * big1, sc, w, sc.rounds.size() + 1, I, stream));  // 2. to 4.
   }
-  return st;
+  return MI_OK;
 }
 
 int mi_radix_mul_batch(const mi_shortint_key* key, uint64_t* radix_out, const uint64_t* lhs, const uint64_t* rhs,
                        size_t n_blocks, size_t n_integers, void* stream) {
-  int st = check_radix(key, radix_out, n_blocks, n_integers);
-  if (st != MI_OK) return st;
-  if ((st = schedule_rules(key->m, key->c)) != MI_OK) return st;
+  MI_TRY(check_radix(key, radix_out, n_blocks, n_integers));
+  MI_TRY(schedule_rules(key->m, key->c));
   if (key->c != key->m)
     return fail(MI_ERR_UNSUPPORTED,
                 "the radix multiplication packs message_modulus * lhs + rhs: carry_modulus must equal message_modulus");
@@ -357,51 +310,40 @@ int mi_radix_mul_batch(const mi_shortint_key* key, uint64_t* radix_out, const ui
     if (p != radix_out && overlap(radix_out, bytes, p, bytes))
       return fail(MI_ERR_INVALID_ARG, "radix_out partially overlaps an operand");
   Schedule sc;
-  if ((st = build_schedule(mul_lengths(B, key->m), key->m, key->c, sc)) != MI_OK) return st;
-  const PassLayout lay = pass_layout(sc, big1, true);
-  size_t per_pass = 0;
-  if ((st = integers_per_pass(sc, lay, NI, &per_pass)) != MI_OK) return st;
+  MI_TRY(plan_passes(key->m, key->c, big1, mul_lengths(B, key->m), true, NI, sc));
   const hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
-  mi::ScratchBuf buf(lay.bytes * per_pass, s);
+  mi::ScratchBuf buf(sc.lay.bytes * sc.per_pass, s);
   if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
   const size_t pairs = B * (B + 1) / 2;
-  for (size_t i0 = 0; i0 < NI && st == MI_OK; i0 += per_pass) {
-    const size_t I = std::min(per_pass, NI - i0), rows = I * B, row_bytes = rows * big1 * sizeof(uint64_t);
-    const Workspace w = carve(buf.ptr(), lay, sc, big1, I);
-    uint64_t* staged = w.tail;
-    uint64_t* pack = staged + 2 * rows * big1;
-    st = hip_status(hipMemcpyAsync(staged, lhs + i0 * B * big1, row_bytes, hipMemcpyDeviceToDevice, s), "radix mul copy");
-    if (st == MI_OK)
-      st = hip_status(hipMemcpyAsync(staged + rows * big1, rhs + i0 * B * big1, row_bytes, hipMemcpyDeviceToDevice, s),
-                      "radix mul copy");
+  for (size_t i0 = 0; i0 < NI; i0 += sc.per_pass) {
+    const size_t I = std::min(sc.per_pass, NI - i0), rows = I * B, row_bytes = rows * big1 * sizeof(uint64_t);
+    const mi::PassWork w = mi::carve_on<mi::PassWork>(buf.ptr(), sc.lay, big1, I);
+    uint64_t *staged = w.tail, *pack = staged + 2 * rows * big1;  // 1. the staged operands, then the packed pairs
+    MI_TRY(stage_pair(staged, lhs + i0 * B * big1, rhs + i0 * B * big1, row_bytes, "radix mul copy", s));
     const mi::MulPairs mp = {(uint32_t)B, (uint32_t)I, key->m > 2 ? 1u : 0u, LUT_MUL_LSB, LUT_MUL_MSB, (int64_t)key->m};
-    if (st == MI_OK)
-      st = hip_status(mi::launch_radix_mul_pairs(w.pack_idx, w.pack_coeff, w.in_idx, w.lut_idx, mp, s),
-                      "radix mul index launch");
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(pack, staged, key->big, 2 * rows, pairs * I, 2, w.pack_idx, w.pack_coeff,
-                                           nullptr, key->device, stream);
-    if (st == MI_OK)
-      st = mi_shortint_apply_lut_batch(key, w.pool, pack, pairs * I, w.in_idx, key->d_luts, w.lut_idx, N_KEY_LUTS,
-                                       (size_t)sc.n_initial * I, stream);
-    if (st == MI_OK) st = run_rounds(key, radix_out + i0 * B * big1, sc, w, I, stream);
+    MI_TRY_HIP(mi::launch_radix_mul_pairs(w.pack_idx, w.pack_coeff, w.in_idx, w.lut_idx, mp, s),
+               "radix mul index launch");
+    MI_TRY(mi_lwe_linear_combination_batch(pack, staged, key->big, 2 * rows, pairs * I, 2, w.pack_idx, w.pack_coeff,
+                                           nullptr, key->device, stream));
+    // 2. the products
+    MI_TRY(mi_shortint_apply_lut_batch(key, w.pool, pack, pairs * I, w.in_idx, key->d_luts, w.lut_idx, N_KEY_LUTS,
+                                       (size_t)sc.n_initial * I, stream));
+    MI_TRY(run_rounds(key, radix_out + i0 * B * big1, sc, w, sc.rounds.size() + 1, I, stream));  // 3.
   }
-  return st;
+  return MI_OK;
 }
 
 int mi_radix_mul_index_arrays(uint64_t message_modulus, uint64_t carry_modulus, size_t n_blocks, size_t n_integers,
                               size_t step, uint32_t* index, int64_t* coeff, uint32_t* in_index, uint32_t* lut_index,
                               size_t capacity, size_t* n_index, size_t* n_items, int device, void* stream) {
   if (n_blocks == 0) return fail(MI_ERR_INVALID_ARG, "n_blocks is 0");
-  int st = schedule_rules(message_modulus, carry_modulus);
-  if (st != MI_OK) return st;
+  MI_TRY(schedule_rules(message_modulus, carry_modulus));
   if (n_blocks > mi::RADIX_MAX_BLOCKS) return too_many_blocks();
   if (!index || !coeff || !in_index || !lut_index) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
-  Schedule sc;
-  if ((st = build_schedule(mul_lengths(n_blocks, message_modulus), message_modulus, carry_modulus, sc)) != MI_OK)
-    return st;
+  Schedule sc;  // no pass here: the arrays are the caller's
+  MI_TRY(build_schedule(mul_lengths(n_blocks, message_modulus), message_modulus, carry_modulus, sc));
   const size_t B = n_blocks, I = n_integers, R = sc.rounds.size(), pairs = B * (B + 1) / 2;
   if (step > R + 1) return fail(MI_ERR_INVALID_ARG, "step is past the block sums");
   // every step up to `step` writes into the caller's arrays
@@ -421,25 +363,13 @@ int mi_radix_mul_index_arrays(uint64_t message_modulus, uint64_t carry_modulus, 
                              (int64_t)message_modulus};
     return hip_status(mi::launch_radix_mul_pairs(index, coeff, in_index, lut_index, mp, s), "radix mul index launch");
   }
-  mi::ScratchBuf buf(2 * (size_t)sc.n_initial * sizeof(uint32_t), s);
+  mi::ScratchBuf buf(2 * (size_t)sc.n_initial * sizeof(uint32_t), s);  // the two lists
   if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-  uint32_t* list[2] = {(uint32_t*)buf.ptr(), (uint32_t*)buf.ptr() + sc.n_initial};
-  const uint32_t* prev = nullptr;
-  for (size_t r = 0; r < std::min(step, R) && st == MI_OK; ++r) {
-    const Round& rd = sc.rounds[r];
-    mi::SumRound d = descriptor(sc, rd.col, I);
-    d.n_chunks = rd.n_chunks, d.n_items = rd.n_items, d.new_total = rd.new_total, d.out_base = rd.out_base;
-    st = hip_status(mi::launch_radix_sum_round(index, in_index, lut_index, list[r & 1], prev, d, LUT_MSG, LUT_CARRY, s),
-                    "radix sum index launch");
-    prev = list[r & 1];
-  }
-  if (st == MI_OK && step == R + 1) {
-    mi::SumRound d = descriptor(sc, sc.last, I);
-    d.final_round = 1;
-    st = hip_status(mi::launch_radix_sum_round(index, nullptr, nullptr, nullptr, prev, d, LUT_MSG, LUT_CARRY, s),
-                    "radix sum index launch");
-  }
-  return st;
+  mi::PassWork w = {};  // the caller's arrays and the two lists
+  w.sum_idx = index, w.in_idx = in_index, w.lut_idx = lut_index;
+  w.list[0] = (uint32_t*)buf.ptr(), w.list[1] = w.list[0] + sc.n_initial;
+  // steps 1 .. R are the rounds and step R + 1 the block sums: the first `step` launches, with nothing in between
+  return run_rounds(nullptr, nullptr, sc, w, step, I, stream);
 }
 
 }  // extern "C"

@@ -81,15 +81,9 @@ int pbs_call(const mi_shortint_key* key, uint64_t* out, const uint64_t* in, cons
 }
 
 // out[j] = in[j] + in[T + j - 1] for block b >= 1, in[j] for block 0, over in = msg[T] | carry-like[T]
-int add_previous(uint64_t* out, const uint64_t* work, size_t big1, size_t blocks, size_t total, uint32_t* ia,
-                 uint32_t* ib, uint32_t* pairs, int device, hipStream_t s) {
+int add_previous(const RadixStages& sg, uint64_t* out, const uint64_t* work, size_t blocks, size_t total) {
   const uint32_t T = (uint32_t)total, B = (uint32_t)blocks;
-  int st = hip_status(mi::launch_index_rule(ia, total, {T, T, 0, 0, 0, 0}, s), "radix index launch");
-  if (st == MI_OK) st = hip_status(mi::launch_index_rule(ib, total, {T, B, 1, T, B, 1}, s), "radix index launch");
-  if (st == MI_OK) st = hip_status(mi::launch_index_pairs(pairs, nullptr, ia, ib, total, 1, 1, s), "radix index launch");
-  if (st == MI_OK)
-    st = mi_lwe_linear_combination_batch(out, work, big1 - 1, 2 * total, total, 2, pairs, nullptr, nullptr, device, s);
-  return st;
+  return sg.combine2(out, work, 2 * total, total, {T, T, 0, 0, 0, 0}, {T, B, 1, T, B, 1});
 }
 
 }  // namespace
@@ -177,8 +171,7 @@ int mi_shortint_key_create(const mi_lwe_ksk* ksk, int pbs_engine, const void* pb
   if (!ksk || !pbs_key) return fail(MI_ERR_INVALID_ARG, "key is NULL");
   size_t ks_in = 0, ks_out = 0, n_lwe = 0, n = 0, ms_dim = 0;
   int k = 1, variant = MI_NTT64_BNF, device = 0;
-  int st = mi_lwe_ksk_info(ksk, &ks_in, &ks_out, nullptr, nullptr);
-  if (st != MI_OK) return st;
+  MI_TRY(mi_lwe_ksk_info(ksk, &ks_in, &ks_out, nullptr, nullptr));
   if (pbs_engine == MI_SHORTINT_PBS_NTT64) {
     const mi_pbs_ntt64_key* p = (const mi_pbs_ntt64_key*)pbs_key;
     n_lwe = p->n_lwe, k = p->k, n = p->plan->n, variant = p->variant, device = p->plan->device;
@@ -191,10 +184,9 @@ int mi_shortint_key_create(const mi_lwe_ksk* ksk, int pbs_engine, const void* pb
   } else {
     return fail(MI_ERR_INVALID_ARG, "unknown pbs engine");
   }
-  if (ms_noise && (st = mi_ms_noise_key_info(ms_noise, &ms_dim, nullptr, nullptr, nullptr, nullptr)) != MI_OK) return st;
-  st = mi_shortint_key_check(ks_in, ks_out, n_lwe, k, n, pbs_engine, variant, ms_noise != nullptr, ms_dim, ms_mode,
-                             message_modulus, carry_modulus);
-  if (st != MI_OK) return st;
+  if (ms_noise) MI_TRY(mi_ms_noise_key_info(ms_noise, &ms_dim, nullptr, nullptr, nullptr, nullptr));
+  MI_TRY(mi_shortint_key_check(ks_in, ks_out, n_lwe, k, n, pbs_engine, variant, ms_noise != nullptr, ms_dim, ms_mode,
+                               message_modulus, carry_modulus));
   // the lookup tables of the radix drivers
   const uint64_t m = message_modulus, sup = message_modulus * carry_modulus;
   const size_t per = ((size_t)k + 1) * n;
@@ -210,8 +202,7 @@ int mi_shortint_key_create(const mi_lwe_ksk* ksk, int pbs_engine, const void* pb
                  : l == LUT_MUL_LSB ? (cur * prev) % m
                                     : (cur * prev) / m;
     }
-    st = mi_shortint_lut_fill(luts.data() + l * per, n, k, message_modulus, carry_modulus, table.data(), sup);
-    if (st != MI_OK) return st;
+    MI_TRY(mi_shortint_lut_fill(luts.data() + l * per, n, k, message_modulus, carry_modulus, table.data(), sup));
   }
   DeviceGuard g(device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
@@ -275,39 +266,30 @@ int mi_shortint_apply_lut_batch(const mi_shortint_key* key, uint64_t* lwe_out, c
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   if (n_in == 0) return MI_OK;  // every in_index is out of range: every item is left untouched
-  const bool drift = key->ms_noise != nullptr;
-  const size_t rows = n_in * (drift ? 2 : 1) + (in_index ? n_items : 0);
-  mi::ScratchBuf buf(rows * small1 * sizeof(uint64_t) + (in_index ? n_items * sizeof(uint32_t) : 0), s);
-  if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-  uint64_t* ks = (uint64_t*)buf.ptr();
-  uint64_t* cur = ks;
-  int st = mi_lwe_keyswitch_batch(key->ksk, ks, lwe_in, n_in, stream);
+  const bool drift = key->ms_noise != nullptr, indexed = in_index != nullptr;
+  MI_CARVED_SCRATCH(mi::ApplyWork, w, s, n_in, n_items, small1, drift, indexed);
+  const uint64_t* cur = w.ks;
   int mode = key->ms_mode;
-  if (st == MI_OK && drift) {
+  MI_TRY(mi_lwe_keyswitch_batch(key->ksk, w.ks, lwe_in, n_in, stream));
+  if (drift) {
     int log2n = 0;
     while (((size_t)1 << log2n) < 2 * key->n) ++log2n;
-    uint64_t* sw = ks + n_in * small1;
-    st = mi_lwe_ms_noise_improve_and_switch_batch(key->ms_noise, sw, ks, n_in, log2n, stream);
-    cur = sw, mode = MI_MS_PRE_SWITCHED;
+    MI_TRY(mi_lwe_ms_noise_improve_and_switch_batch(key->ms_noise, w.sw, w.ks, n_in, log2n, stream));
+    cur = w.sw, mode = MI_MS_PRE_SWITCHED;
   }
   const uint32_t* idx = lut_index;
-  if (st == MI_OK && in_index) {
-    uint64_t* gathered = ks + n_in * (drift ? 2 : 1) * small1;
-    uint32_t* eff = (uint32_t*)(gathered + n_items * small1);
-    st = mi_lwe_linear_combination_batch(gathered, cur, key->small_, n_in, n_items, 1, in_index, nullptr, nullptr,
-                                         key->device, stream);
-    if (st == MI_OK)
-      st = hip_status(mi::launch_mask_lut_index(eff, in_index, lut_index, n_in, n_items, s), "apply lut index launch");
-    cur = gathered, idx = eff;
+  if (indexed) {
+    MI_TRY(mi_lwe_linear_combination_batch(w.gathered, cur, key->small_, n_in, n_items, 1, in_index, nullptr, nullptr,
+                                           key->device, stream));
+    MI_TRY_HIP(mi::launch_mask_lut_index(w.eff, in_index, lut_index, n_in, n_items, s), "apply lut index launch");
+    cur = w.gathered, idx = w.eff;
   }
-  if (st == MI_OK) st = pbs_call(key, lwe_out, cur, lut_list, idx, n_lut, n_items, mode, stream);
-  return st;
+  return pbs_call(key, lwe_out, cur, lut_list, idx, n_lut, n_items, mode, stream);
 }
 
 int mi_radix_propagate_single_carry_batch(const mi_shortint_key* key, uint64_t* radix, uint64_t* carry_out,
                                           size_t n_blocks, size_t n_integers, void* stream) {
-  int st = check_radix(key, radix, n_blocks, n_integers);
-  if (st != MI_OK) return st;
+  MI_TRY(check_radix(key, radix, n_blocks, n_integers));
   if (n_blocks > 1 && !single_carry_supported(key->m, key->c)) return single_carry_unsupported();
   if (n_integers == 0) return MI_OK;
   const size_t B = n_blocks, I = n_integers, T = I * B, big1 = key->big + 1;
@@ -318,104 +300,57 @@ int mi_radix_propagate_single_carry_batch(const mi_shortint_key* key, uint64_t* 
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   const uint32_t t32 = (uint32_t)T, b32 = (uint32_t)B;
-  // work = msg[T] | st[T]; pack / sum [T]; index arrays: in[2 T], lut[2 T], a[T], b[T], pairs[2 T]; coeff[2 T]
-  mi::ScratchBuf buf(3 * T * big1 * sizeof(uint64_t) + 2 * T * sizeof(int64_t) + 8 * T * sizeof(uint32_t), s);
-  if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-  uint64_t* work = (uint64_t*)buf.ptr();
-  uint64_t* stt = work + T * big1;
-  uint64_t* pack = work + 2 * T * big1;
-  int64_t* coeff = (int64_t*)(pack + T * big1);
-  uint32_t* in_idx = (uint32_t*)(coeff + 2 * T);
-  uint32_t* lut_idx = in_idx + 2 * T;
-  uint32_t* ia = lut_idx + 2 * T;
-  uint32_t* ib = ia + T;
-  uint32_t* pairs = ib + T;
-  const uint64_t* luts = key->d_luts;
-  const char* what = "radix index launch";
-  // round 1: the message and the state of every block, one keyswitch per block
-  const bool want_state = B > 1 || carry_out;
-  const size_t items1 = want_state ? 2 * T : T;
-  st = hip_status(mi::launch_index_rule(in_idx, items1, {t32, t32, 0, 0, 0, 0}, s), what);
-  if (st == MI_OK) st = hip_status(mi::launch_lut_rule(lut_idx, items1, T, LUT_MSG, B, LUT_STATE0, LUT_STATE, s), what);
-  if (st == MI_OK)
-    st = mi_shortint_apply_lut_batch(key, work, radix, T, in_idx, luts, lut_idx, N_KEY_LUTS, items1, stream);
+  MI_CARVED_SCRATCH(mi::SingleCarryWork, w, s, T, big1);
+  const RadixStages sg{key, s, w.ix};
+  uint64_t* st = w.work + T * big1;
+  const mi::IndexRule row_mod_t = {t32, t32, 0, 0, 0, 0};
+  // 1. the message and the state of every block, one keyswitch per block (the state only where something reads it)
+  const size_t items1 = B > 1 || carry_out ? 2 * T : T;
+  MI_TRY(sg.apply(w.work, radix, T, items1, &row_mod_t, T, LUT_MSG, B, LUT_STATE0, LUT_STATE));
   if (B == 1) {  // nothing to propagate into: the message, and the state of block 0 is the carry
-    const uint64_t* res = work;
-    if (st == MI_OK) st = hip_status(mi::launch_index_rule(ia, T, {t32, t32, 0, 0, 0, 0}, s), what);
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(radix, res, key->big, T, T, 1, ia, nullptr, nullptr, key->device, stream);
-    if (st == MI_OK && carry_out) {
-      st = hip_status(mi::launch_index_rule(ib, T, {t32, t32, 0, t32, 0, 0}, s), what);
-      if (st == MI_OK)
-        st = mi_lwe_linear_combination_batch(carry_out, res, key->big, 2 * T, T, 1, ib, nullptr, nullptr, key->device,
-                                             stream);
-    }
-    return st;
+    MI_TRY(sg.gather(radix, w.work, T, T, row_mod_t));
+    if (carry_out) MI_TRY(sg.gather(carry_out, w.work, 2 * T, T, {t32, t32, 0, t32, 0, 0}));
+    return MI_OK;
   }
-  // the scan rounds
-  for (size_t sp = 1; sp < B && st == MI_OK; sp *= 2) {
-    const uint32_t s32 = (uint32_t)sp, rem = b32 - s32;
-    const size_t cnt = I * (B - sp);
-    const uint32_t c32 = (uint32_t)cnt;
-    st = hip_status(mi::launch_index_rule(ia, cnt, {c32, rem, 0, t32 + s32, b32, 0}, s), what);
-    if (st == MI_OK) st = hip_status(mi::launch_index_rule(ib, cnt, {c32, rem, 0, t32, b32, 0}, s), what);
-    if (st == MI_OK) st = hip_status(mi::launch_index_pairs(pairs, coeff, ia, ib, cnt, (int64_t)key->m, 1, s), what);
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(pack, work, key->big, 2 * T, cnt, 2, pairs, coeff, nullptr, key->device,
-                                           stream);
-    if (st == MI_OK) st = hip_status(mi::launch_index_rule(in_idx, T, {t32, b32, s32, 0, rem, s32}, s), what);
-    if (st == MI_OK) st = hip_status(mi::launch_lut_rule(lut_idx, T, T, LUT_SCAN, 1, LUT_SCAN, LUT_SCAN, s), what);
-    if (st == MI_OK)
-      st = mi_shortint_apply_lut_batch(key, stt, pack, cnt, in_idx, luts, lut_idx, N_KEY_LUTS, T, stream);
+  // 2. the scan rounds
+  for (size_t sp = 1; sp < B; sp *= 2) {
+    const uint32_t s32 = (uint32_t)sp, rem = b32 - s32, c32 = (uint32_t)(I * (B - sp));
+    MI_TRY(sg.combine2(w.pack, w.work, 2 * T, c32, {c32, rem, 0, t32 + s32, b32, 0}, {c32, rem, 0, t32, b32, 0},
+                       (int64_t)key->m, 1));
+    const mi::IndexRule packed_row = {t32, b32, s32, 0, rem, s32};
+    MI_TRY(sg.apply(st, w.pack, c32, T, &packed_row, T, LUT_SCAN, 1, LUT_SCAN, LUT_SCAN));
   }
-  // the last round: message + carry of the block below
-  if (st == MI_OK) st = add_previous(pack, work, big1, B, T, ia, ib, pairs, key->device, s);
-  if (st == MI_OK) st = hip_status(mi::launch_lut_rule(lut_idx, T, T, LUT_MSG, 1, LUT_MSG, LUT_MSG, s), what);
-  if (st == MI_OK) st = mi_shortint_apply_lut_batch(key, radix, pack, T, nullptr, luts, lut_idx, N_KEY_LUTS, T, stream);
-  if (st == MI_OK && carry_out) {
-    st = hip_status(mi::launch_index_rule(ia, I, {(uint32_t)I, 1, 0, t32 + b32 - 1, b32, 0}, s), what);
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(carry_out, work, key->big, 2 * T, I, 1, ia, nullptr, nullptr, key->device,
-                                           stream);
-  }
-  return st;
+  // 3. message + carry of the block below
+  MI_TRY(add_previous(sg, w.pack, w.work, B, T));
+  MI_TRY(sg.apply(radix, w.pack, T, T, nullptr, T, LUT_MSG, 1, LUT_MSG, LUT_MSG));
+  if (carry_out)  // 4.
+    MI_TRY(sg.gather(carry_out, w.work, 2 * T, I, {(uint32_t)I, 1, 0, t32 + b32 - 1, b32, 0}));
+  return MI_OK;
 }
 
 int mi_radix_full_propagate_batch(const mi_shortint_key* key, uint64_t* radix, size_t n_blocks, size_t n_integers,
                                   void* stream) {
-  int st = check_radix(key, radix, n_blocks, n_integers);
-  if (st != MI_OK) return st;
+  MI_TRY(check_radix(key, radix, n_blocks, n_integers));
   if (n_integers == 0) return MI_OK;
   const hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   const size_t B = n_blocks, T = n_integers * B, big1 = key->big + 1;
   const bool single = B == 1 || single_carry_supported(key->m, key->c);
-  mi::ScratchBuf buf(2 * T * big1 * sizeof(uint64_t) + 8 * T * sizeof(uint32_t), s);
-  if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-  uint64_t* work = (uint64_t*)buf.ptr();
-  uint32_t* in_idx = (uint32_t*)(work + 2 * T * big1);
-  uint32_t* lut_idx = in_idx + 2 * T;
-  uint32_t* ia = lut_idx + 2 * T;
-  uint32_t* ib = ia + T;
-  uint32_t* pairs = ib + T;
-  const size_t rounds = single ? 1 : B;
-  for (size_t r = 0; r < rounds && st == MI_OK; ++r) {
-    st = hip_status(mi::launch_index_rule(in_idx, 2 * T, {(uint32_t)T, (uint32_t)T, 0, 0, 0, 0}, s), "radix index launch");
-    if (st == MI_OK)
-      st = hip_status(mi::launch_lut_rule(lut_idx, 2 * T, T, LUT_MSG, 1, LUT_CARRY, LUT_CARRY, s), "radix index launch");
-    if (st == MI_OK)
-      st = mi_shortint_apply_lut_batch(key, work, radix, T, in_idx, key->d_luts, lut_idx, N_KEY_LUTS, 2 * T, stream);
-    if (st == MI_OK) st = add_previous(radix, work, big1, B, T, ia, ib, pairs, key->device, s);
+  MI_CARVED_SCRATCH(mi::TwoListWork, w, s, T, big1, 2 * T);
+  const RadixStages sg{key, s, w.ix};
+  const mi::IndexRule row_mod_t = {(uint32_t)T, (uint32_t)T, 0, 0, 0, 0};
+  for (size_t r = 0; r < (single ? 1 : B); ++r) {
+    MI_TRY(sg.apply(w.both, radix, T, 2 * T, &row_mod_t, T, LUT_MSG, 1, LUT_CARRY, LUT_CARRY));  // 1.
+    MI_TRY(add_previous(sg, radix, w.both, B, T));                                                // 2.
   }
-  if (st == MI_OK && single && B > 1) st = mi_radix_propagate_single_carry_batch(key, radix, nullptr, B, n_integers, stream);
-  return st;
+  if (single && B > 1) return mi_radix_propagate_single_carry_batch(key, radix, nullptr, B, n_integers, stream);  // 3.
+  return MI_OK;
 }
 
 int mi_radix_add_batch(const mi_shortint_key* key, uint64_t* radix_out, const uint64_t* lhs, const uint64_t* rhs,
                        uint64_t* carry_out, size_t n_blocks, size_t n_integers, void* stream) {
-  int st = check_radix(key, radix_out, n_blocks, n_integers);
-  if (st != MI_OK) return st;
+  MI_TRY(check_radix(key, radix_out, n_blocks, n_integers));
   if (n_blocks > 1 && !single_carry_supported(key->m, key->c)) return single_carry_unsupported();
   if (n_integers == 0) return MI_OK;
   if (!lhs || !rhs) return fail(MI_ERR_INVALID_ARG, "buffer is NULL");
@@ -430,26 +365,13 @@ int mi_radix_add_batch(const mi_shortint_key* key, uint64_t* radix_out, const ui
   DeviceGuard g(key->device);
   if (!g.ok) return fail(MI_ERR_INVALID_ARG, "bad device");
   {
-    mi::ScratchBuf buf(2 * bytes + 4 * T * sizeof(uint32_t), s);
-    if (!buf.ok()) return fail(MI_ERR_OOM, "scratch allocation failed");
-    uint64_t* both = (uint64_t*)buf.ptr();
-    uint32_t* ia = (uint32_t*)(both + 2 * T * big1);
-    uint32_t* ib = ia + T;
-    uint32_t* pairs = ib + T;
+    MI_CARVED_SCRATCH(mi::TwoListWork, w, s, T, big1, (size_t)0);
+    const RadixStages sg{key, s, w.ix};
     const uint32_t t32 = (uint32_t)T;
-    st = hip_status(hipMemcpyAsync(both, lhs, bytes, hipMemcpyDeviceToDevice, s), "radix add copy");
-    if (st == MI_OK)
-      st = hip_status(hipMemcpyAsync(both + T * big1, rhs, bytes, hipMemcpyDeviceToDevice, s), "radix add copy");
-    if (st == MI_OK) st = hip_status(mi::launch_index_rule(ia, T, {t32, t32, 0, 0, 0, 0}, s), "radix index launch");
-    if (st == MI_OK) st = hip_status(mi::launch_index_rule(ib, T, {t32, t32, 0, t32, 0, 0}, s), "radix index launch");
-    if (st == MI_OK)
-      st = hip_status(mi::launch_index_pairs(pairs, nullptr, ia, ib, T, 1, 1, s), "radix index launch");
-    if (st == MI_OK)
-      st = mi_lwe_linear_combination_batch(radix_out, both, key->big, 2 * T, T, 2, pairs, nullptr, nullptr, key->device,
-                                           stream);
+    MI_TRY(stage_pair(w.both, lhs, rhs, bytes, "radix add copy", s));
+    MI_TRY(sg.combine2(radix_out, w.both, 2 * T, T, {t32, t32, 0, 0, 0, 0}, {t32, t32, 0, t32, 0, 0}));
   }
-  if (st == MI_OK) st = mi_radix_propagate_single_carry_batch(key, radix_out, carry_out, n_blocks, n_integers, stream);
-  return st;
+  return mi_radix_propagate_single_carry_batch(key, radix_out, carry_out, n_blocks, n_integers, stream);
 }
 
 }  // extern "C"
